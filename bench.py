@@ -10,10 +10,20 @@ work   : per GPU B_u = 256 unlabeled + N_s = 32 labeled 64x64 samples
          (highres codec, ROM 8x8, the factory's Dropout2d rate 0.2), weak
          scaling over GPUs.
 
-Usage: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no
-torch.distributed environment, this process starts ``torch.distributed.run
---nproc-per-node N`` as a CHILD (before it touches the GPU) and relays rank 0's
-JSON line; under torchrun (WORLD_SIZE set) WORLD_SIZE must equal N.
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].
+With N > 1 and no torch.distributed environment, this process starts
+``torch.distributed.run --nproc-per-node N`` as a CHILD (before it touches the
+GPU) and relays rank 0's JSON line; under torchrun (WORLD_SIZE set) WORLD_SIZE
+must equal N.
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR  after the timed steps, what the last timed step left with its
+         caller (parameters, gradient, Adam moments, ELBO) as DIR/<name>.npy;
+         the inputs are seeded, so equal arguments give equal inputs.
+--full   also the per-operator HIP-event profile with the roofline of the
+         dominant launch (--kprof FILE writes the profile; --no-roofline skips
+         both) and the CPU baseline (--no-cpu-baseline skips it); without
+         --full the line's ``roofline`` and ``cpu_baseline`` are null.
 """
 import argparse
 import json
@@ -378,6 +388,29 @@ def conv_source_sha():
     return h.hexdigest()
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000     # all files of one --dump-outputs together
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(path, step, elbo):
+    """What the last timed step left with its caller, as path/<name>.npy: the flat parameter vector after the
+    step's Adam update, the step's finalised gradient, Adam's two moment vectors (float32, the model's own
+    flat layout: shared parameters first, then the labeled samples' variational rows) and the step's ELBO
+    (float64).  An array over its share of DUMP_BUDGET_BYTES is stored as a fixed, seeded sample of its
+    elements (ascending flat indices, the same for every run of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {'params': step.flat.P, 'grad': step.flat.G, 'adam_m': step.m, 'adam_v': step.v}
+    share = (DUMP_BUDGET_BYTES - 1024) // len(arrays)
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().reshape(-1).cpu().numpy().astype(np.float32, copy=False))
+        if a.nbytes > share - 1024:             # (1 KiB per file for the .npy header)
+            keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, (share - 1024) // 4, replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + '.npy'), a)
+    np.save(os.path.join(path, 'elbo.npy'), np.array([elbo], dtype=np.float64))
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(('127.0.0.1', 0))
@@ -415,9 +448,14 @@ def main():
     # 4 steps per replay: 0.5726 / 0.5728 vs 0.5768 / 0.5773 ms per step with 1 (r04l, one box)
     ap.add_argument('--unroll', type=int, default=int(os.environ.get('GPI_UNROLL', '4')),
                     help="steps per graph replay ('streams' graph mode; FusedElboStep.capture(unroll))")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--kprof', default=None, help='write the per-operator HIP-event profile (JSON) here')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one left with its caller as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also the per-operator profile + roofline and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: no per-operator profile / roofline')
+    ap.add_argument('--kprof', default=None,
+                    help='with --full: write the per-operator HIP-event profile (JSON) here')
     ap.add_argument('--sync-bn', action='store_true',
                     help='SyncBN: BN statistics over the union of the ranks\' batches (default replica-BN; at N = 1 '
                          'a one-rank process group, to time the exchange)')
@@ -434,6 +472,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
+    if args.kprof and (not args.full or args.no_roofline):
+        raise SystemExit('--kprof needs the per-operator profile: run with --full (and without --no-roofline)')
     if 'WORLD_SIZE' not in os.environ:
         if args.gpus > 1:
             sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -506,9 +548,12 @@ def main():
     cpu = None
     per_step = B_u + N_s
     ms_step = 1e3 * dt / args.steps
-    sbytes, sparts = step_bytes(model, B_u, N_s, physics)
     log('timed %d steps: %.4f ms/step' % (args.steps, ms_step))
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step, elbo)
+        log('outputs written to %s' % args.dump_outputs)
+    if rank == 0 and args.full and not args.no_roofline:
+        sbytes, sparts = step_bytes(model, B_u, N_s, physics)
         prof = profile_kernels(step)
         log('per-operator profile done')
         if args.kprof:
@@ -556,7 +601,7 @@ def main():
                     codec_ms_sum=round(sum(t[1] for t in prof), 4),
                     step=dict(bytes=sbytes, achieved=round(step_ach, 1), frac=round(step_ach / HBM_PEAK_GBS, 4),
                               **sparts))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log('cpu baseline')
         cpu = cpu_baseline(model, data, B_u, N_s, physics)
 
@@ -566,7 +611,7 @@ def main():
             'metric': 'ELBO training-step samples/sec (64x64 grids)' if args.config == 'c64' else
             'ELBO training-step samples/sec (%s)' % args.config,
             'value': round(value, 1), 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(ms_step, 4), 'higher_is_better': True,
+            'warmup': args.warmup, 'ms_per_step': round(ms_step, 4), 'higher_is_better': True, 'full': args.full,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'config': {'workload': 'BASELINE config %s: %s grid, B_u=%d unlabeled + N_s=%d labeled per GPU, '
                                    'ROM %dx%d, fused native step' % (CONFIG_TAG[args.config], args.config, B_u, N_s,

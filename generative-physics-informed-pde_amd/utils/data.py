@@ -9,6 +9,8 @@ stencil, separable random-field sampler); otherwise on the host (scipy).  ``Data
 on a subset of indices with device-cached tensors and the reference's
 ``get(key, random_subset)`` semantics (utils/data.py:419-445).
 """
+import os
+
 import numpy as np
 import torch
 
@@ -76,7 +78,7 @@ class DataLoader(object):
     def save(self, path):
         """torch.save of {'X': double [N, py, px], ...} (utils/data.py:284-291); the NDP
         encodings are stored beside the images so labels can be re-assembled identically."""
-        if len(path.split('.')) == 1:
+        if not os.path.splitext(os.path.basename(path))[1]:     # the file's own name: a directory may hold a dot
             raise ValueError(path)
         torch.save({'X': torch.tensor(self.X), 'U': torch.tensor(self.BCE.U)}, path)
 

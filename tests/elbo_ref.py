@@ -18,8 +18,34 @@ CODEC = {32: dict(blocks=[1, 1], growth=4, f0=4), 64: dict(blocks=[1, 2, 1], gro
 _PHYS = {}
 
 
+FIELD_CHECK_STRIDE = 1021     # every 1021st pixel of a seeded input array is stored with its fixture
+
+
+def random_fields(gen, n_img, n):
+    """Smooth-ish log-conductivity images (separable SE correlation), float64: the fixtures' input fields
+    (tests/golden/make_golden.py draws them from ``gen`` with this function).  The contraction runs as two
+    matrix products (optimize=True: 0.05 s instead of 9 s for 256 images of 64x64); the summation order differs
+    from the plain einsum's at the 1e-15 level, far below the fp32 the fixtures store their inputs in."""
+    x = (np.arange(n) + 0.5) / n
+    C = np.exp(-0.5 * (x[:, None] - x[None, :]) ** 2 / 0.15 ** 2) + 1e-6 * np.eye(n)
+    L = np.linalg.cholesky(C)
+    G = gen.normal(size=(n_img, n, n))
+    return 0.4 + 0.8 * np.einsum('ij,bjk,lk->bil', L, G, L, optimize=True)
+
+
 def load(name):
-    return dict(np.load(os.path.join(GOLD, name), allow_pickle=False))
+    """A golden fixture as a dict.  A fixture with 'field_seed' (elbo_c64.npz) stores its input fields Xu, Xs
+    as the seed of the generator they were the first two draws of (5 MB of fp32 images otherwise); they are
+    drawn again here and checked against the strided sample of them that the fixture keeps ('Xu_check',
+    'Xs_check': equal to fp32 rounding)."""
+    d = dict(np.load(os.path.join(GOLD, name), allow_pickle=False))
+    if 'field_seed' in d:
+        n, _, _, Nu, _, Ns = [int(v) for v in d['cfg']]
+        rng = np.random.default_rng(int(d['field_seed']))
+        for key, count in (('Xu', Nu), ('Xs', Ns)):
+            d[key] = random_fields(rng, count, n).astype(np.float32)
+            np.testing.assert_allclose(d[key].ravel()[::FIELD_CHECK_STRIDE], d[key + '_check'], rtol=0, atol=5e-7)
+    return d
 
 
 def physics(nc, r):

@@ -39,6 +39,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = '/root/reference'
 sys.path.insert(0, ROOT)
 from oracle import fem  # noqa: E402
+sys.path.insert(0, os.path.dirname(HERE))
+from elbo_ref import random_fields, FIELD_CHECK_STRIDE  # noqa: E402  (the tests draw seeded input fields again)
 
 for m in ['fenics', 'dolfin', 'petsc4py', 'petsc4py.PETSc', 'prettytable']:
     sys.modules[m] = mock.MagicMock()
@@ -71,15 +73,6 @@ def randomize_bn(module, gen):
             if isinstance(m, torch.nn.BatchNorm2d):
                 m.weight.copy_(1.0 + 0.3 * torch.randn(m.weight.shape, generator=gen))
                 m.bias.copy_(0.2 * torch.randn(m.bias.shape, generator=gen))
-
-
-def random_fields(gen, n_img, n):
-    # smooth-ish log-conductivity images (separable SE correlation)
-    x = (np.arange(n) + 0.5) / n
-    C = np.exp(-0.5 * (x[:, None] - x[None, :]) ** 2 / 0.15 ** 2) + 1e-6 * np.eye(n)
-    L = np.linalg.cholesky(C)
-    G = gen.normal(size=(n_img, n, n))
-    return 0.4 + 0.8 * np.einsum('ij,bjk,lk->bil', L, G, L)
 
 
 # --------------------------------------------------------------------------
@@ -361,11 +354,14 @@ def make_elbo_c64():
     """GenerativeModel.elbo (armortized + supervised freeX) + backward at the BENCHMARKED shape:
     highres codec (d_z 64, blocks [1, 2, 1], growth 4, init features 6), ROM 8x8 on 64x64,
     B_u = 256 armortized samples out of a pool of 256 (random order), N_s = 32 labeled
-    -> elbo_c64.npz.  ~5 MB: inputs stored in fp32, M / W rebuilt from the oracle by the tests."""
+    -> elbo_c64.npz.  ~1 MB: the input fields Xu, Xs (5 MB in fp32) are stored as their generator's seed
+    ('field_seed': they are its first two draws) with every FIELD_CHECK_STRIDE-th pixel as a check, and
+    elbo_ref.load draws them again; M / W are rebuilt from the oracle by the tests."""
     phys = c64_physics()
     nc, r, mc, mf, M, W, cdofs, fdofs = phys
     n = nc * r
-    rng = np.random.default_rng(64)
+    field_seed = 64
+    rng = np.random.default_rng(field_seed)
     Nu, bs, Ns, dz = 256, 256, 32, 64
     gen = torch.Generator().manual_seed(65)
     model, g = _elbo_model(phys, n, dz, [1, 2, 1], 4, 6, gen)
@@ -388,7 +384,8 @@ def make_elbo_c64():
     elbo, gr = _elbo_run(model, perm, eps, armortized_bs=bs)
     out = {'state.' + k: v for k, v in state0.items()}
     out.update({'grad.' + k: v for k, v in gr.items()})
-    out.update(Xu=Xu.numpy(), Xs=Xs_img, Y=Y.astype(np.float32), F=F.astype(np.float32), U=U,
+    out.update(field_seed=np.int64(field_seed), Xu_check=Xu.numpy().ravel()[::FIELD_CHECK_STRIDE],
+               Xs_check=Xs_img.ravel()[::FIELD_CHECK_STRIDE], Y=Y.astype(np.float32), F=F.astype(np.float32), U=U,
                perm=perm.numpy(), eps_enc=eps[0].numpy(), eps_qz=eps[1].numpy(), eps_qX=eps[2].numpy(),
                elbo=np.float64(elbo.item()), bc_dofs=cdofs, cfg=np.array([n, nc, dz, Nu, bs, Ns]))
     np.savez_compressed(os.path.join(HERE, 'elbo_c64.npz'), **out)

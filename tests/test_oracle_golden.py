@@ -320,8 +320,8 @@ def test_elbo_c64():
     reference's fp32 CPU run (elbo_c64.npz): value 1e-5; gradients by elbo_ref.check_grads (the reference's
     own fp32 run flips a few near-tie ReLUs of the encoder: ~3e-3 on the tensors upstream of them, ~3e-6
     elsewhere)."""
-    from elbo_ref import oracle_fixture_elbo, tensor_rel, check_grads
-    d = load('elbo_c64.npz')
+    from elbo_ref import oracle_fixture_elbo, tensor_rel, check_grads, load as load_seeded
+    d = load_seeded('elbo_c64.npz')        # (draws the fixture's input fields again from their seed)
     val, gr = oracle_fixture_elbo(d)
     assert abs(val - float(d['elbo'])) <= 1e-5 * abs(float(d['elbo']))
     assert set(gr) == {k[5:] for k in d if k.startswith('grad.')}

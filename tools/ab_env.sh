@@ -21,7 +21,7 @@ i=0
 for E in "$@"; do
     i=$((i + 1))
     [ "$E" = "-" ] && E=""
-    env $E timeout -k 10 200 python -u bench.py --steps ${AB_STEPS:-300} --warmup 30 --no-cpu-baseline \
+    env $E timeout -k 10 200 python -u bench.py --full --steps ${AB_STEPS:-300} --warmup 30 --no-cpu-baseline \
         --kprof "$OUT/kprof_${TAG}_$i.json" > "$OUT/bench_${TAG}_$i.log" 2> "$OUT/bench_${TAG}_$i.err"
     rc=$?
     echo "[$i] ${E:-defaults}: $(tail -1 "$OUT/bench_${TAG}_$i.log" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"])' 2>/dev/null)"

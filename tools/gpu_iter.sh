@@ -52,7 +52,7 @@ if [ -n "${IT_PHASE:-}" ]; then
     [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${IT_BENCH:-0}" = "1" ]; then
-    timeout -k 10 400 python bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.log"
+    timeout -k 10 400 python bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.log"
     rc=$?; tail -1 "$OUT/bench_$TAG.json"; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${IT_PROF:-0}" = "1" ]; then

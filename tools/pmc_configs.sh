@@ -26,7 +26,7 @@ for CFG in "$@"; do
     P=${TPFX:-r05}
     if [ "$CFG" = "c64" ]; then TF=${P}_traffic.json; else TF=${P}_traffic_$CFG.json; fi
     cp "$OUT/traffic_${TAG}_$CFG.json" "$R/profiles/$TF"
-    timeout -k 10 300 python3 bench.py --config "$CFG" --steps 50 --warmup 10 > "$OUT/bench_${TAG}_$CFG.json" \
+    timeout -k 10 300 python3 bench.py --full --config "$CFG" --steps 50 --warmup 10 > "$OUT/bench_${TAG}_$CFG.json" \
         2> "$OUT/bench_${TAG}_$CFG.err"
     rc=$?; echo "$CFG bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
     cd /tmp

@@ -7,7 +7,7 @@ mkdir -p "$R/gpurun_out/sweep"
 for cfg in "$@"; do
     set -- $cfg
     tag="f$1_b$2_s$3"
-    GPI_TILE_FWD=$1 GPI_TILE_BWD=$2 GPI_TILE_S2=$3 timeout -k 10 120 python "$R/bench.py" --steps 50 --warmup 10 \
+    GPI_TILE_FWD=$1 GPI_TILE_BWD=$2 GPI_TILE_S2=$3 timeout -k 10 120 python "$R/bench.py" --full --steps 50 --warmup 10 \
         --no-cpu-baseline --kprof "$R/gpurun_out/sweep/$tag.json" > "$R/gpurun_out/sweep/$tag.log" 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "$tag rc=$rc"; tail -3 "$R/gpurun_out/sweep/$tag.log"; exit $rc; fi

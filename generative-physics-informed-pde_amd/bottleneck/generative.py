@@ -398,7 +398,27 @@ class DiscriminativeModel(lamp.modules.BaseModule):
     def curtail(self):
         self._encoder = None
 
+    def predictor(self, B):
+        """The gpi.infer.SurrogatePredictor of this model for batch size B (cached per B)."""
+        from gpi.infer import SurrogatePredictor
+        if self._encoder is None:
+            raise RuntimeError('a curtailed DiscriminativeModel has no encoder to predict from')
+        cache = self.__dict__.setdefault('_gpi_predictors', {})
+        p = cache.get(B)
+        if p is None or p.enc is not self._encoder or not all(p.flat.owns(q) for q in self._encoder.parameters()):
+            p = cache[B] = SurrogatePredictor(self, B)
+        return p
+
+    @torch.no_grad()
+    def predict_mc(self, x, F, N_mc, eps=None):
+        """(mean, std) [B, d_y] of the MC predictive y at the encoder's eval-mode (mu, logsigma)."""
+        return self.predictor(x.shape[0]).predict_mc(x, F, N_mc, eps=eps)
+
     def forward(self, x, F):
+        if not self.training and self._encoder is not None:
+            # inference: eval-mode encoder -> gp mean -> ROM on the surrogate predictor (no autograd graph)
+            mean = self.predictor(x.shape[0]).predict(x, F).clone()
+            return mean, self._g.logsigmas_y.detach().repeat(mean.shape[0], 1)
         if self._encoder is not None:
             x = self._encoder(x)[0]
         return self._g(self._gp(x), F=F)

@@ -68,6 +68,11 @@ class BnRunningItem(C.Structure):
                 ('num_batches_tracked', vp)]
 
 
+class BnEvalItem(C.Structure):
+    _fields_ = [('stat', i64), ('channels', i32), ('_pad', i32), ('count', C.c_double), ('running_mean', vp),
+                ('running_var', vp)]
+
+
 class CodecCtx(C.Structure):
     _fields_ = [('params', vp), ('ws', vp), ('stats', vp), ('gacc', vp), ('wpart', vp),
                 ('ext_in', vp), ('ext_idx', vp), ('ext_stride', i64),
@@ -205,7 +210,8 @@ class BnExchangeDesc(C.Structure):
 
 STRUCTS = [Stat, Groups, ConvDesc, CodecCtx, ReduceItem, HeadDesc, GemmItem, RomDesc, ResidualDesc, AdamDesc,
            VoQueryDesc, VoMomentsDesc, VoConditionDesc, VoPrecisionDesc, GpSampleDesc,
-           VoGalerkinDesc, StepEpilogueDesc, FomDesc, RandomFieldDesc, VoSparse, DrawItem, BnExchangeDesc]
+           VoGalerkinDesc, StepEpilogueDesc, FomDesc, RandomFieldDesc, VoSparse, DrawItem, BnExchangeDesc,
+           BnEvalItem]
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -219,6 +225,8 @@ SIGNATURES = {
     'gpi_error_string': (C.c_char_p, [C.c_int]),
     'gpi_conv_blocks': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(Groups), C.POINTER(i32)]),
     'gpi_bn_running_update': (C.c_int, [vp, C.c_int, C.c_int, vp, i64, f32, vp]),
+    'gpi_bn_eval_seed': (C.c_int, [vp, C.c_int, C.c_int, vp, i64, vp]),
+    'gpi_affine': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     'gpi_conv_loss_fused': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(CodecCtx), vp]),
     'gpi_conv_launch_info': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(Groups), C.c_int, C.POINTER(i32)]),
     'gpi_conv_forward': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(CodecCtx), vp]),

@@ -47,6 +47,15 @@ def engine_for(module, key, build):
     return e
 
 
+def eval_engine(module, kind, B, flat):
+    """The eval-mode (inference) engine of an encoder / decoder in .eval(): running-statistic BN, no
+    dropout, no running update, no autograd graph (gpi/infer.py).  Cached next to the train-mode
+    engine of the same batch size: the key carries the mode, the two never share a workspace."""
+    from .infer import EvalEncoderEngine, EvalDecoderEngine
+    cls = EvalEncoderEngine if kind == 'enc' else EvalDecoderEngine
+    return engine_for(module, (kind, B, id(flat), 'eval'), lambda: cls(module, flat, B))
+
+
 def _deliver(flat, scale=None):
     tmp = torch.empty_like(flat.G)
     L.check(L.lib().gpi_grad_finalize(L.ptr(flat.gacc), L.ptr(tmp), flat.numel, L.FINALIZE_ZERO, None,
@@ -92,7 +101,9 @@ def encoder_forward(enc, x):
     dev = x.device
     flat = module_flat(enc, dev)
     B = x.shape[0]
-    e = engine_for(enc, ('enc', B, id(flat)), lambda: EncoderEngine(enc, flat, B))
+    if not enc.training:
+        return eval_engine(enc, 'enc', B, flat).forward(x)
+    e = engine_for(enc, ('enc', B, id(flat), 'train'), lambda: EncoderEngine(enc, flat, B))
     drop = _take_injected(enc)
     return EncoderFunction.apply(anchor(enc, dev), x, e, drop, _seed() if (e.p.drop_numel and drop is None) else 0)
 
@@ -117,7 +128,9 @@ def decoder_forward(dec, z):
     dev = z.device
     flat = module_flat(dec, dev)
     B = z.shape[0]
-    e = engine_for(dec, ('dec', B, id(flat)), lambda: DecoderEngine(dec, flat, B))
+    if not dec.training:
+        return eval_engine(dec, 'dec', B, flat).forward(z.detach().contiguous().float())
+    e = engine_for(dec, ('dec', B, id(flat), 'train'), lambda: DecoderEngine(dec, flat, B))
     drop = _take_injected(dec)
     return DecoderFunction.apply(anchor(dec, dev), z, e, drop, _seed() if (e.p.drop_numel and drop is None) else 0)
 

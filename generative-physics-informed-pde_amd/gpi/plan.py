@@ -96,18 +96,28 @@ class CodecProgram(object):
         return op
 
     # ------------------------------------------------------------ lowering
-    def layout(self, B, ws, stats, parts, groups, param_offset, grad=True):
-        """Assign workspace / stat / partial-slab offsets for batch B."""
+    def layout(self, B, ws, stats, parts, groups, param_offset, grad=True, eval_mode=False):
+        """Assign workspace / stat / partial-slab offsets for batch B.
+        eval_mode (inference, gpi/infer.py): every BN-consuming conv gets its OWN range of cin stat
+        records (op.in_stat; each nn.BatchNorm2d has its own running buffers, also where several
+        layers read the same channels of a dense block), no conv writes statistics (GPI_EPI_STORE
+        where training has STORE_STATS, out_stat -1), no Dropout2d (drop_off -1), and nothing that
+        only the backward reads is allocated (implies grad=False)."""
+        if eval_mode:
+            grad = False
         for b in self.buffers:
             if b.external:
                 continue
             b.off = ws.alloc(B * b.per_sample)
-            if b.bn_consumed:
+            if b.bn_consumed and not eval_mode:
                 b.stat = stats.alloc(b.C) if isinstance(stats, Arena) else None
+        if eval_mode:
+            for op in self.ops:
+                op.in_stat = stats.alloc(op.cin) if op.bn is not None else -1
         # Dropout2d channel scales [B][cout] of every dropout op, one contiguous region
         self.drop_off = ws.size
         for op in self.ops:
-            if op.drop:
+            if op.drop and not eval_mode:
                 op.drop_off = ws.alloc(B * op.cout)
         self.drop_numel = ws.size - self.drop_off
         # backward buffers
@@ -138,17 +148,17 @@ class CodecProgram(object):
             if op.bn is not None:
                 d.gamma_off = param_offset(op.bn + '.weight')
                 d.beta_off = param_offset(op.bn + '.bias')
-                d.in_stat = op.src.stat + op.c0
+                d.in_stat = op.in_stat if eval_mode else op.src.stat + op.c0
             else:
                 d.gamma_off = d.beta_off = d.in_stat = -1
             d.w_off = param_offset(op.w)
             d.out_off = op.dst.off
             d.out_ctot, d.out_c0 = op.dst.C, op.d0
-            d.out_stat = (op.dst.stat + op.d0) if op.dst.bn_consumed else -1
+            d.out_stat = (op.dst.stat + op.d0) if (op.dst.bn_consumed and not eval_mode) else -1
             if op.epilogue is not None:
                 d.epilogue = op.epilogue
             else:
-                d.epilogue = L.EPI_STORE_STATS if op.dst.bn_consumed else L.EPI_STORE
+                d.epilogue = L.EPI_STORE_STATS if (op.dst.bn_consumed and not eval_mode) else L.EPI_STORE
             d.gout_mode = 0 if op.dst.bn_consumed else 1
             d.gout_off = op.dst.s_off if op.dst.s_off is not None else -1
             if op.bn is not None or (not op.src.external and op.src.s_off is not None):
@@ -161,7 +171,7 @@ class CodecProgram(object):
             op.numel = op.cout * op.cin * op.k * op.k
             op.rowlen = op.numel + (2 * op.cin if op.bn is not None else 0)
             d.wpart_off = parts.alloc(op.blocks * op.rowlen) if grad else -1
-            d.drop_off = op.drop_off if op.drop else -1
+            d.drop_off = op.drop_off if (op.drop and not eval_mode) else -1
             op.desc = d
             descs.append(d)
         arr = (L.ConvDesc * len(descs))(*descs)

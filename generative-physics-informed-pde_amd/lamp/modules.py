@@ -7,6 +7,27 @@ from lamp.utils import get_default_device, get_default_dtype, get_device, get_dt
 class BaseModule(torch.nn.Module):
     """torch.nn.Module + state()/load()/_to() helpers used across the reference."""
 
+    def __deepcopy__(self, memo):
+        """copy.deepcopy without the native caches (_gpi_flat / _gpi_engines / _gpi_anchor / ... on this
+        module and every submodule): engines and flat buffers hold device pointers of THIS module's
+        tensors, so a copy that kept them would share -- or, through its engines, overwrite -- the
+        original's workspaces.  The copy owns plain tensors and builds its own caches at its first call."""
+        import copy
+        held = []
+        for m in self.modules():
+            for k in [k for k in m.__dict__ if k.startswith('_gpi_')]:
+                held.append((m, k, m.__dict__.pop(k)))
+        # (an instance attribute shadows this method for the nested call: the default reduce-based copy runs)
+        object.__setattr__(self, '__deepcopy__', None)
+        try:
+            new = copy.deepcopy(self, memo)
+        finally:
+            del self.__dict__['__deepcopy__']
+            for m, k, v in held:
+                m.__dict__[k] = v
+        new.__dict__.pop('__deepcopy__', None)
+        return new
+
     @property
     def num_parameters(self):
         return sum(p.numel() for p in self.parameters())

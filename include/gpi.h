@@ -481,6 +481,31 @@ typedef struct gpi_bn_running_item {
 int gpi_bn_running_update(const gpi_bn_running_item* items, int n_items, int max_channels, const gpi_stat* stats,
                           int64_t n_stats, float momentum, void* stream);
 
+/* Eval-mode BatchNorm2d (inference): seeds the forward fields of the statistics records so that the
+ * forward kernels' relu(BN) on load normalises with the layer's RUNNING statistics.  For every item
+ * (one BN layer: `channels` records from `stat`, its own range -- in eval every nn.BatchNorm2d has its
+ * own buffers, also where several layers read the same channels of a dense block) and channel c:
+ *   sum = count * running_mean[c],  sumsq = count * (running_var[c] + running_mean[c]^2)
+ * in replica 0 of group 0, zero in the other replicas; count = samples * H * W is the element count the
+ * consuming launch divides by, so that it recovers running_mean exactly and 1 / sqrt(running_var + eps) to
+ * fp32 rounding.  The backward fields are not touched.  Plain stores (one thread per record).
+ * items: device array of n_items records (persistent, graph-capture safe); null or empty arguments
+ * return GPI_ERR_ARG and launch nothing. */
+typedef struct gpi_bn_eval_item {
+    int64_t stat;
+    int32_t channels, _pad;
+    double count;
+    const float* running_mean;
+    const float* running_var;
+} gpi_bn_eval_item;
+int gpi_bn_eval_seed(const gpi_bn_eval_item* items, int n_items, int max_channels, gpi_stat* stats, int64_t n_stats,
+                     void* stream);
+
+/* out[r][m] = b[m] + sum_k W[m][k] in[r][k] (row-major fp32, fp64 accumulation; b may be NULL): the
+ * deterministic effective-property map z -> gp mean of the surrogate predictor (no noise drawn or read). */
+int gpi_affine(const float* W, const float* b, const float* in, float* out, int rows, int d_out, int d_in,
+               void* stream);
+
 /* SyncBN exchange of one BN seam (the fp64 BN sums of stat slots [stat0, stat0 + n), fields f0 and f0 + 1, of
  * every BN group; ElboEngine.set_sync_bn, codec.py:164-173 at the union batch).  One 64-thread launch:
  *   GPI_BNX_FOLD    msg[g][c][f] = the GPI_REPLICAS copies summed in replica order (the caller all-reduces msg,

@@ -18,7 +18,11 @@ Samplers on the native path, concatenated in the reference's order:
 CoarseGrainedResidualSampler (infinite precision), FluxConstrainSampler
 (learnable precision), GaussianSketchingSampler and RadialBasisFunctionSampler
 (infinite precision, test functions redrawn on the device at every resample).
-The energy VOs (host numpy loops in the reference) are not native and raise.
+
+The energy VOs (vo_spec['type'] = 'energy'; dense host numpy loops per VO sample and
+inner iteration in the reference) run as gpi_vo_energy (csrc/energy.hip): matrix-free
+subspace corrections of a persistent batched fp64 mean, RBF centres drawn on the
+device, with the reference's temperature schedules on the host.
 """
 import numpy as np
 import torch
@@ -881,9 +885,309 @@ class VirtualObservablesEnsemble(BaseVirtualObservablesEnsemble):
                                   global_step=iteration)
 
 
-class EnergyVirtualObservablesEnsemble(BaseVirtualObservablesEnsemble):
-    """Energy VOs (VirtualObservables.py:672-793,1001-1037) run numpy loops on the host in the
-    reference and are outside the native ELBO path (SURVEY.md section 8 lists the constrain VOs)."""
+# ---------------------------------------------------------------------------
+class TemperatureSchedule(object):
+    """VirtualObservables.py:1040-1046."""
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError('energy virtual observables are not on the native path')
+    def __init__(self):
+        pass
+
+    def get_temperature(self, iteration):
+        raise NotImplementedError
+
+
+class LinearTemperatureSchedule(TemperatureSchedule):
+    """T_init + it / (num_steps - 1) (T_final - T_init)  (VirtualObservables.py:1050-1068, quirks kept:
+    the fraction's denominator, and ``it == num_steps`` still answers, one step past T_final)."""
+
+    def __init__(self, T_init, T_final, num_steps):
+        super().__init__()
+        assert num_steps > 1
+        assert T_final < T_init
+        self._T_init = T_init
+        self._T_final = T_final
+        self._num_steps = num_steps
+
+    def get_temperature(self, iteration):
+        if iteration > self._num_steps:
+            raise RuntimeError
+        frac = iteration / (self._num_steps - 1)
+        return self._T_init + frac * (self._T_final - self._T_init)
+
+
+class ExponentialTemperatureSchedule(TemperatureSchedule):
+    """T_init exp(-lambda it / (num_steps - 1)), lambda = -log(T_final / T_init)
+    (VirtualObservables.py:1071-1091)."""
+
+    def __init__(self, T_init, T_final, num_steps):
+        super().__init__()
+        assert num_steps > 1
+        assert T_final < T_init
+        self._T_init = T_init
+        self._T_final = T_final
+        self._num_steps = num_steps
+        self._lmbda = - np.log(T_final / T_init)
+
+    def get_temperature(self, iteration):
+        if iteration > self._num_steps:
+            raise RuntimeError
+        t = iteration / (self._num_steps - 1)
+        return self._T_init * np.exp(-self._lmbda * t)
+
+
+class _EnergyTemperature(object):
+    """Temperature of the energy VOs (EnergyVirtualObservable, VirtualObservables.py:692-766): the
+    reference keeps one copy per VO sample and sets them all alike; here the ensemble owns one and
+    its members delegate to it."""
+
+    def __init__(self):
+        self.value = 1
+        self.schedule = None
+        self.forced = None
+
+    @property
+    def current(self):
+        return self.value if self.forced is None else self.forced
+
+    def set(self, temperature):
+        assert temperature >= 0
+        self.value = temperature
+
+    def set_schedule(self, type, T_init, T_final, num_steps):
+        assert type.lower() in ['linear', 'exponential']
+        if type.lower() == 'linear':
+            self.schedule = LinearTemperatureSchedule(T_init, T_final, num_steps)
+        else:
+            self.schedule = ExponentialTemperatureSchedule(T_init, T_final, num_steps)
+
+    def set_linear_schedule(self, T_init=1, T_final=0.0001, num_steps=None):
+        if num_steps is None:
+            raise ValueError
+        self.schedule = LinearTemperatureSchedule(T_init, T_final, num_steps)
+
+    def update(self, iteration):
+        if self.forced is not None:
+            return
+        if self.schedule is None:
+            raise RuntimeError
+        self.value = self.schedule.get_temperature(iteration)
+
+
+class _EnergyState(object):
+    """Batched device state of N energy VO samples: the persistent fp64 mean, vars, their model-dtype
+    mirrors, the skipped-iteration flag and the one gpi_vo_energy launch that updates them."""
+
+    def __init__(self, x_dg, bc, n_fine, num_iterations, m_aux, length, device):
+        N, dy = x_dg.shape[0], (n_fine + 1) * (n_fine - 1)
+        self.x_dg, self.bc, self.n_fine = x_dg, bc, n_fine
+        self.num_iterations, self.m_aux, self.length = int(num_iterations), int(m_aux), float(length)
+        self.mean64 = torch.zeros(N, dy, dtype=torch.float64, device=device)     # _init(): zeros once
+        self.vars64 = torch.zeros(N, dy, dtype=torch.float64, device=device)
+        self.mean32 = torch.zeros(N, dy, dtype=torch.float32, device=device)
+        self.logsig32 = torch.zeros(N, dy, dtype=torch.float32, device=device)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self.form = L.VO_ENERGY_AUTO
+        self.work = None
+        self.centers = []           # injected centres [n_iter, N, m_aux, 2], one entry per coming update
+        self.has_posterior = False
+
+    def update(self, G, PREC, temperature):
+        centers = self.centers.pop(0) if self.centers else None
+        self.work = V.vo_energy(self.x_dg, self.bc, self.n_fine, G.detach().to(torch.float32).contiguous(),
+                                PREC.detach().to(torch.float32).contiguous(), temperature, self.mean64,
+                                self.vars64, self.m_aux, self.num_iterations, self.length, mean32=self.mean32,
+                                logsig32=self.logsig32, centers=centers, seed=_host_seed(), flag=self.flag,
+                                form=self.form, work=self.work)
+        self.has_posterior = True
+
+
+def _energy_sampler_sizes(sampler):
+    if not isinstance(sampler, RadialBasisFunctionSampler):
+        raise NotImplementedError(
+            'energy virtual observables draw their test functions on the device and take only this '
+            "package's RadialBasisFunctionSampler (its m and length are read); got %s" % type(sampler).__name__)
+    return sampler.m, sampler._length
+
+
+class EnergyVirtualObservable(BaseVirtualObservable):
+    """VirtualObservables.py:672-793.  ``mean`` / ``vars`` are fp64 views of the rows of the batched state
+    (the ensemble's, or a batch of one for a VO used on its own); None before the first update."""
+
+    def __init__(self, querry_point, num_iterations_per_update, stochastic_subspace=None, sampler=None, l=0.1,
+                 dtype=None, device=None, _state=None, _index=0, _temperature=None):
+        if dtype is None or device is None:
+            raise ValueError('need to provide dtype and device')
+        super().__init__(querry_point, dtype=dtype, device=device)
+        self._stochastic_subspace = stochastic_subspace
+        self._num_iterations_per_update = num_iterations_per_update
+        if sampler is None:
+            if stochastic_subspace is None:
+                raise ValueError
+            sampler = RadialBasisFunctionSampler(self._querry_point, l=l, N_aux=stochastic_subspace, device=device)
+        self._sampler = sampler
+        self._m_aux, self._length = _energy_sampler_sizes(sampler)
+        self._T = _temperature if _temperature is not None else _EnergyTemperature()
+        self._state, self._index = _state, _index
+
+    def _own_state(self):
+        if self._state is None:
+            qp = self._querry_point
+            n = int(round(np.sqrt(qp.dim_in / 2)))
+            x = torch.tensor(qp.x, dtype=torch.float64, device=self.device).view(1, -1).contiguous()
+            u = torch.tensor(qp.u, dtype=torch.float64, device=self.device).view(1, 4).contiguous()
+            self._state = _EnergyState(x, u, n, self._num_iterations_per_update, self._m_aux, self._length,
+                                       self.device)
+            self._index = 0
+        return self._state
+
+    @property
+    def temperature(self):
+        return self._T.current
+
+    @property
+    def _temperature(self):
+        return self._T.value
+
+    def force_temperature(self, value):
+        self._T.forced = value
+
+    @property
+    def mean(self):
+        st = self._state
+        return st.mean64[self._index] if st is not None and st.has_posterior else None
+
+    @property
+    def vars(self):
+        st = self._state
+        return st.vars64[self._index] if st is not None and st.has_posterior else None
+
+    @property
+    def m(self):
+        return 1
+
+    def resample(self, ForceResample=False):
+        # nothing to be done (the test functions are redrawn inside every update)
+        pass
+
+    def set_temperature(self, temperature):
+        self._T.set(temperature)
+
+    def set_temperature_schedule(self, type, T_init, T_final, num_steps):
+        self._T.set_schedule(type, T_init, T_final, num_steps)
+
+    def set_linear_temperature_schedule(self, T_init=1, T_final=0.0001, num_steps=None):
+        self._T.set_linear_schedule(T_init, T_final, num_steps)
+
+    def update_precision(self, iteration):
+        self._T.update(iteration)
+
+    @torch.no_grad()
+    def update(self, g, prec, iteration, *, ForceUpdate=False):
+        """VirtualObservables.py:769-788 for this sample alone (a batch of one native launch)."""
+        if not ForceUpdate:
+            raise RuntimeError
+        st = self._own_state()
+        if st.mean64.shape[0] != 1:
+            raise RuntimeError('a member of an energy VO ensemble is updated through the ensemble')
+        st.update(g.reshape(1, -1), prec.reshape(1, -1), self.temperature)
+
+    def __repr__(self):
+        s = 'Energy virtual Observable | Current temperature = {}'.format(self._temperature)
+        return s
+
+
+class EnergyVirtualObservablesEnsemble(BaseVirtualObservablesEnsemble):
+    """VirtualObservables.py:1001-1037 with batched device state (mean64 / vars64 / mean32 / logsig32
+    [N, d_y]) and one gpi_vo_energy launch set per update for all VO samples (the reference loops numpy
+    over the samples, a dense d_y x d_y matrix each).  ``sampler`` must be this package's
+    RadialBasisFunctionSampler: its m and length are read, the centres are drawn on the device."""
+
+    def __init__(self, QuerryPointEnsemble, num_iterations_per_update, sampler, dtype, device):
+        m_aux, length = _energy_sampler_sizes(sampler)
+        qp0 = QuerryPointEnsemble[0]
+        n_fine = int(round(np.sqrt(qp0.dim_in / 2)))
+        x, u = QuerryPointEnsemble.device_batch(device)
+        self._state = _EnergyState(x, u, n_fine, num_iterations_per_update, m_aux, length, device)
+        self._T = _EnergyTemperature()
+        vos = [EnergyVirtualObservable(qp, num_iterations_per_update, sampler=sampler, dtype=dtype, device=device,
+                                       _state=self._state, _index=n, _temperature=self._T)
+               for n, qp in enumerate(QuerryPointEnsemble)]
+        super().__init__(QuerryPointEnsemble, vos, dtype=dtype, device=device)
+
+    # ------------------------------------------------------------------ temperature
+    @property
+    def temperature(self):
+        return self._T.current
+
+    def force_temperature(self, value):
+        self._T.forced = value
+
+    def set_temperature(self, *args, **kwargs):
+        self._T.set(*args, **kwargs)
+
+    def set_temperature_schedule(self, type, **kwargs):
+        self._T.set_schedule(type, **kwargs)
+
+    def set_linear_temperature_schedule(self, *args, **kwargs):
+        self._T.set_linear_schedule(*args, **kwargs)
+
+    def update_vo_precision(self, iteration, writer=None):
+        self._T.update(iteration)
+        if writer is not None:
+            writer.add_scalar('Monitoring/Temperature', self._T.current, global_step=iteration)
+
+    # ------------------------------------------------------------------ posterior
+    @property
+    def mean64(self):
+        return self._state.mean64
+
+    @property
+    def vars64(self):
+        return self._state.vars64
+
+    @property
+    def mean32(self):
+        return self._state.mean32
+
+    @property
+    def logsig32(self):
+        return self._state.logsig32
+
+    @property
+    def mean(self):
+        st = self._state
+        if not st.has_posterior:
+            return None
+        return st.mean32.detach() if self.dtype == torch.float32 else st.mean64.to(self.dtype)
+
+    @property
+    def vars(self):
+        st = self._state
+        if not st.has_posterior:
+            return None
+        return st.vars64.to(self.dtype)
+
+    @property
+    def logsigma(self):
+        st = self._state
+        if not st.has_posterior:
+            return None
+        return st.logsig32 if self.dtype == torch.float32 else 0.5 * torch.log(self.vars)
+
+    def queue_centers(self, centers):
+        """Inject the RBF centres [n_iter, N, m_aux, 2] (fp64, device) of the next update not yet spoken
+        for (tests: replaying a recorded run); updates without queued centres draw on the device."""
+        self._state.centers.append(centers)
+
+    @torch.no_grad()
+    def update(self, G, PREC, iteration, writer=None):
+        self.update_vo_precision(iteration, writer)
+        self._state.update(G, PREC, self._T.current)
+        self.flush_cache()
+
+    def check_flag(self):
+        """Lazy report of skipped iterations (host sync): the reference's numpy solve fails or returns
+        garbage on a singular V^T A V; the kernel leaves the mean unchanged and sets the flag."""
+        if int(self._state.flag.item()) != 0:
+            raise RuntimeError('energy VO: an iteration met a singular V^T A V (coincident test functions) '
+                               'and was skipped')

@@ -18,6 +18,7 @@
 //   vo_columns_kernel                 posterior mean / variance per column (|L^-1 Gamma_i|^2, blocked GEMM)
 //   vo_precision_kernel               beta / mean VO variances (deterministic row reductions)
 #include "common.h"
+#include "vo_grid.h"
 
 using namespace gpi;
 
@@ -27,25 +28,6 @@ namespace {
 struct FineGrid {
     int n, nc, r, dy, nn_c, nT_c;
 };
-
-__device__ __forceinline__ double kcell(const double* lk, int n, int i, int j, int ul) {
-    return exp(lk[2 * (i + n * j) + ul]);
-}
-// conductance of the horizontal edge (i,j)-(i+1,j): the lower-right triangle of square (i,j)
-// and the upper-left triangle of square (i,j-1) (P1 on right triangles: -1/2 kappa per leg)
-__device__ __forceinline__ double ch_(const double* lk, int n, int i, int j) {
-    double c = 0.0;
-    if (j < n) c += kcell(lk, n, i, j, 0);
-    if (j > 0) c += kcell(lk, n, i, j - 1, 1);
-    return 0.5 * c;
-}
-// vertical edge (i,j)-(i,j+1): upper-left of square (i,j), lower-right of square (i-1,j)
-__device__ __forceinline__ double cv_(const double* lk, int n, int i, int j) {
-    double c = 0.0;
-    if (i < n) c += kcell(lk, n, i, j, 1);
-    if (i > 0) c += kcell(lk, n, i - 1, j, 0);
-    return 0.5 * c;
-}
 
 // P1 prolongation weights of fine node (i,j) onto the coarse "/" mesh (components.py:42-60)
 __device__ __forceinline__ void interp_w(int i, int j, int r, int nc, int (&k)[3], double (&w)[3]) {
@@ -58,11 +40,6 @@ __device__ __forceinline__ void interp_w(int i, int j, int r, int nc, int (&k)[3
     k[2] = n00 + (nc + 1) + 1;
     if (xi >= eta) { k[1] = n00 + 1; w[0] = 1.0 - xi; w[1] = xi - eta; w[2] = eta; }
     else { k[1] = n00 + (nc + 1); w[0] = 1.0 - eta; w[1] = eta - xi; w[2] = xi; }
-}
-
-__device__ __forceinline__ double bc_value(const double* u, int i, int j, int n) {
-    const double y = (double)j / (double)n;
-    return i == 0 ? u[0] * (1.0 - y) + u[1] * y : u[2] * (1.0 - y) + u[3] * y;
 }
 
 constexpr int NZ = 16;   // nonzeros of one CGR column: 5 stencil nodes x 3 coarse weights

@@ -166,6 +166,18 @@ class VoGalerkinDesc(C.Structure):
                 ('seed', u64), ('offset', vp), ('sub', u64), ('gamma', vp), ('alpha', vp), ('m', i32), ('row0', i32)]
 
 
+VO_ENERGY_AUTO, VO_ENERGY_FUSED, VO_ENERGY_TILED = 0, 1, 2
+VO_ENERGY_MAX_AUX = 32
+
+
+class VoEnergyDesc(C.Structure):
+    _fields_ = [('n_fine', i32), ('n', i32), ('m_aux', i32), ('n_iter', i32), ('form', i32), ('_pad', i32),
+                ('logkappa', vp), ('bc', vp), ('g', vp), ('prec', vp), ('temperature', C.c_double),
+                ('length', C.c_double), ('seed', u64), ('offset', vp), ('sub', u64), ('centers', vp),
+                ('centers_out', vp), ('mean', vp), ('vars', vp), ('mean32', vp), ('logsig32', vp), ('flag', vp),
+                ('work', vp)]
+
+
 class StepEpilogueDesc(C.Structure):
     _fields_ = [('gacc', vp), ('grad', vp), ('n', i64), ('flags', i32), ('n_terms', i32), ('step', vp),
                 ('scratch', vp), ('n_scratch', i64), ('terms_dst', vp), ('idx_src', vp), ('idx_dst', vp),
@@ -211,7 +223,7 @@ class BnExchangeDesc(C.Structure):
 STRUCTS = [Stat, Groups, ConvDesc, CodecCtx, ReduceItem, HeadDesc, GemmItem, RomDesc, ResidualDesc, AdamDesc,
            VoQueryDesc, VoMomentsDesc, VoConditionDesc, VoPrecisionDesc, GpSampleDesc,
            VoGalerkinDesc, StepEpilogueDesc, FomDesc, RandomFieldDesc, VoSparse, DrawItem, BnExchangeDesc,
-           BnEvalItem]
+           BnEvalItem, VoEnergyDesc]
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -273,6 +285,9 @@ SIGNATURES = {
     'gpi_vo_precision': (C.c_int, [C.POINTER(VoPrecisionDesc), vp]),
     'gpi_vo_pattern': (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     'gpi_vo_sparse_values': (C.c_int, [vp, i32, i32, i32, C.POINTER(VoSparse), vp]),
+    'gpi_vo_energy_form': (C.c_int, [i32, i32]),
+    'gpi_vo_energy_workspace': (i64, [i32, i32, i32]),
+    'gpi_vo_energy': (C.c_int, [C.POINTER(VoEnergyDesc), vp]),
     'gpi_gauss_sample': (C.c_int, [vp, vp, vp, i64, i32, i32, vp, u64, vp, u64, vp]),
     'gpi_gp_sample': (C.c_int, [C.POINTER(GpSampleDesc), vp]),
     'gpi_predictive_scores': (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
@@ -285,11 +300,13 @@ INCLUDE_H = os.path.join(os.path.dirname(os.path.dirname(HERE)), 'include', 'gpi
 
 def source_sha():
     """sha1 of the library's sources as csrc/Makefile computes it (csrc/*.hip in name order, csrc/common.h,
-    include/gpi.h, concatenated); None when the sources are not next to the package."""
+    csrc/conv_shapes.h, csrc/vo_grid.h, include/gpi.h, concatenated); None when the sources are not next to the
+    package."""
     import glob
     import hashlib
     files = sorted(glob.glob(os.path.join(SRC_DIR, '*.hip')), key=os.path.basename)
-    files += [os.path.join(SRC_DIR, 'common.h'), os.path.join(SRC_DIR, 'conv_shapes.h'), INCLUDE_H]
+    files += [os.path.join(SRC_DIR, 'common.h'), os.path.join(SRC_DIR, 'conv_shapes.h'),
+              os.path.join(SRC_DIR, 'vo_grid.h'), INCLUDE_H]
     if not all(os.path.exists(f) for f in files):
         return None
     h = hashlib.sha1()

@@ -1,4 +1,4 @@
-"""Launchers of the virtual-observable kernels (csrc/vo.hip, include/gpi.h).
+"""Launchers of the virtual-observable kernels (csrc/vo.hip, csrc/energy.hip, include/gpi.h).
 
 Every function takes device tensors, launches on the current stream and never
 synchronises the host; shapes are checked here, before any launch, against
@@ -215,6 +215,62 @@ def vo_precision(gamma, alpha, mean, vars_, infinite, beta, vo_var, alpha0=ALPHA
     if sparse is not None:
         assert sparse.shape == (N, m, dy)
     L.check(L.lib().gpi_vo_precision(C.byref(d), L.stream_handle()), 'vo precision')
+
+
+ENERGY_SUB = 41  # Philox stream of the energy VO centres (no other VO launch draws from it)
+
+
+def vo_energy_form(n_fine, m_aux):
+    """The kernel form VO_ENERGY_AUTO selects (L.VO_ENERGY_FUSED / L.VO_ENERGY_TILED); host query."""
+    f = L.lib().gpi_vo_energy_form(int(n_fine), int(m_aux))
+    if f < 0:
+        L.check(f, 'gpi_vo_energy_form')
+    return f
+
+
+def vo_energy_workspace(n_fine, n, m_aux, device):
+    """Workspace of the tiled form for n samples (fp64 device tensor)."""
+    k = L.lib().gpi_vo_energy_workspace(int(n_fine), int(n), int(m_aux))
+    if k < 0:
+        L.check(int(k), 'gpi_vo_energy_workspace')
+    return torch.empty(max(int(k), 1), dtype=torch.float64, device=device)
+
+
+def vo_energy(x_dg, bc, n_fine, g, prec, temperature, mean, vars_, m_aux, n_iter, length, mean32=None,
+              logsig32=None, centers=None, centers_out=None, seed=0, offset=None, sub=ENERGY_SUB, flag=None,
+              form=L.VO_ENERGY_AUTO, work=None):
+    """EnergyVirtualObservable.update for every VO sample (VirtualObservables.py:769-788): n_iter subspace
+    corrections of ``mean`` [N, d_y] (fp64, in/out) towards the solution of (diag(prec) + K / T) y =
+    f / T + prec * g over m_aux fresh RBF test functions per sample and iteration, and ``vars_`` =
+    1 / (prec + diag(K) / T).  ``centers`` [n_iter, N, m_aux, 2] injects the RBF centres (else device
+    Philox, recorded into ``centers_out`` when given).  Returns the workspace it used (or None)."""
+    _dev(x_dg, bc, g, prec, mean, vars_, mean32, logsig32, centers, centers_out, offset, flag, work)
+    N = x_dg.shape[0]
+    dy = (n_fine + 1) * (n_fine - 1)
+    assert x_dg.shape == (N, 2 * n_fine * n_fine) and bc.shape == (N, 4)
+    assert x_dg.dtype == torch.float64 and bc.dtype == torch.float64
+    assert g.shape == (N, dy) and prec.shape == (N, dy) and g.dtype == torch.float32 and prec.dtype == torch.float32
+    assert mean.shape == (N, dy) and vars_.shape == (N, dy)
+    assert mean.dtype == torch.float64 and vars_.dtype == torch.float64
+    for t, dt in ((mean32, torch.float32), (logsig32, torch.float32)):
+        assert t is None or (t.shape == (N, dy) and t.dtype == dt)
+    for t in (centers, centers_out):
+        assert t is None or (t.shape == (n_iter, N, m_aux, 2) and t.dtype == torch.float64)
+    assert flag is None or (flag.dtype == torch.int32 and flag.numel() >= 1)
+    assert offset is None or offset.dtype == torch.int64 or offset.dtype == torch.uint64
+    for t in (x_dg, bc, g, prec, mean, vars_, mean32, logsig32, centers, centers_out):
+        assert t is None or t.is_contiguous()
+    if form == L.VO_ENERGY_TILED or (form == L.VO_ENERGY_AUTO and vo_energy_form(n_fine, m_aux) == L.VO_ENERGY_TILED):
+        need = L.lib().gpi_vo_energy_workspace(int(n_fine), N, int(m_aux))
+        if work is None:
+            work = vo_energy_workspace(n_fine, N, m_aux, x_dg.device)
+        assert work.dtype == torch.float64 and work.is_contiguous() and work.numel() >= need
+    d = L.VoEnergyDesc(n_fine=n_fine, n=N, m_aux=m_aux, n_iter=n_iter, form=form, logkappa=_p(x_dg), bc=_p(bc),
+                       g=_p(g), prec=_p(prec), temperature=float(temperature), length=float(length), seed=seed,
+                       offset=_p(offset), sub=sub, centers=_p(centers), centers_out=_p(centers_out), mean=_p(mean),
+                       vars=_p(vars_), mean32=_p(mean32), logsig32=_p(logsig32), flag=_p(flag), work=_p(work))
+    L.check(L.lib().gpi_vo_energy(C.byref(d), L.stream_handle()), 'vo energy')
+    return work
 
 
 def gauss_sample(out, mean, logsigma, rep=1, eps=None, seed=0, offset=None, sub=0, stream=None):

@@ -401,6 +401,50 @@ typedef struct gpi_vo_precision_desc {
     const gpi_vo_sparse* sparse; /* optional column-sparse view of gamma (then gamma itself is not read) */
 } gpi_vo_precision_desc;
 
+/* Energy virtual observables (EnergyVirtualObservable.update, VirtualObservables.py:769-788): per VO
+ * sample, with beta = 1 / temperature, K / f the fine free-node stiffness and load of the sample,
+ *   vars = 1 / (prec + beta diag(K)),   A = diag(prec) + beta K,   b = beta f + prec * g,
+ *   n_iter times:  mean <- mean - V (V^T A V)^-1 V^T (A mean - b),
+ * V [d_y, m_aux] fresh RBF test functions exp(-|x - c|^2 / length^2) on the free nodes per sample and
+ * iteration.  Matrix-free: K by the 5-point stencil of edge conductances, f on the two
+ * Dirichlet-adjacent columns, V from per-axis tables; fp64, every reduction in a fixed order (bitwise
+ * reproducible), no host synchronisation.  Centre a of (iteration it, sample s) is `centers[it, s, a]`
+ * or Philox at counter *offset + ((it * n + s) * m_aux + a), stream `sub`, key `seed`:
+ * cx = x 2^-32, cy = y 2^-32.  An iteration whose V^T A V has a Cholesky pivot <= 1e-12 of its
+ * diagonal entry (coincident centres) is skipped for that sample and *flag is set.
+ * form: AUTO the first that applies of FUSED (one workgroup per sample runs all iterations, mean and
+ * conductances LDS-resident; needs 8 (d_y + 2 n_fine^2 + 2 m8 (n_fine + 1) + m8^2 + 4 m8 + 288) bytes,
+ * m8 = m_aux rounded up to 8, within the 160 KiB of a CU) and TILED (any grid whose tables fit: per
+ * iteration a partial-sum, a solve and an update launch over (row tile, sample), state in `work`);
+ * an explicit form that does not apply returns GPI_ERR_UNSUPPORTED. */
+#define GPI_VO_ENERGY_AUTO  0
+#define GPI_VO_ENERGY_FUSED 1
+#define GPI_VO_ENERGY_TILED 2
+#define GPI_VO_ENERGY_MAX_AUX 32
+#define GPI_VO_ENERGY_MAX_ITER 4096
+
+typedef struct gpi_vo_energy_desc {
+    int32_t n_fine, n, m_aux, n_iter, form, _pad;
+    const double* logkappa;    /* [n, 2 n_fine^2] */
+    const double* bc;          /* [n, 4] */
+    const float* g;            /* [n, d_y] prior mean */
+    const float* prec;         /* [n, d_y] prior precision */
+    double temperature;        /* > 0 */
+    double length;             /* RBF length scale l > 0 */
+    uint64_t seed;
+    const uint64_t* offset;    /* device Philox offset (may be NULL = 0) */
+    uint64_t sub;
+    const double* centers;     /* optional [n_iter, n, m_aux, 2] injected centres */
+    double* centers_out;       /* optional [n_iter, n, m_aux, 2]: the centres used */
+    double* mean;              /* [n, d_y] in/out: the persistent state */
+    double* vars;              /* [n, d_y] out */
+    float* mean32;             /* optional [n, d_y] out: (float) mean */
+    float* logsig32;           /* optional [n, d_y] out: 0.5 log((float) vars), the log taken in fp64 and
+                                  rounded once */
+    int32_t* flag;             /* optional: set to 1 when an iteration was skipped */
+    double* work;              /* TILED: gpi_vo_energy_workspace(...) doubles (FUSED: unused, may be NULL) */
+} gpi_vo_energy_desc;
+
 /* Predictive effective properties (Analysis.sample_predictive_y's first two stages,
  * components.py:472-478 + EffectivePropertyMap.propagate_samples :238-249): for row r,
  * j = r / rep,  z = qz_mu[j] + exp(qz_ls[j]) eps_z,  x = gp_w z + gp_b (+ exp(gp_ls) eps_x when
@@ -612,6 +656,12 @@ int gpi_vo_pattern(const double* gamma, int32_t n, int32_t m, int32_t d_y, int32
 int gpi_vo_sparse_values(const double* gamma, int32_t n, int32_t m, int32_t d_y, const gpi_vo_sparse* sp,
                          void* stream);
 int gpi_vo_precision(const gpi_vo_precision_desc* d, void* stream);
+/* Energy VO update.  gpi_vo_energy_form: the form AUTO selects for a grid (GPI_VO_ENERGY_FUSED / _TILED,
+ * or a negative error); gpi_vo_energy_workspace: doubles of `work` the TILED form needs for n samples
+ * (or a negative error).  Both are host queries and launch nothing. */
+int gpi_vo_energy_form(int32_t n_fine, int32_t m_aux);
+int64_t gpi_vo_energy_workspace(int32_t n_fine, int32_t n, int32_t m_aux);
+int gpi_vo_energy(const gpi_vo_energy_desc* d, void* stream);
 /* Reparametrised Gaussian rows (bottleneck/utils.py:216-219, components.py:174-180):
  * out[r, t] = mean[r / rep, t] + exp(logsigma[r / rep, t]) * N(0,1), normals from
  * Philox counter (*offset + r * dim + t) in stream `sub` (or eps[r, t] if eps != NULL). */

@@ -116,7 +116,8 @@ struct ConvGeom {
     int ph;         // owned input rows (backward)
     const float* zero;   // the zero page (kernel argument: no per-use address reload)
     int zreg;       // backward: the BN-backward operand z of the output in registers (<= ZREG chunks / thread)
-    int npx;        // forward: horizontally adjacent output pixels per thread (1, 2, 4)
+    int npx;        // forward: horizontally adjacent output pixels per thread (1, 2, 4), or NPX_ROWS2: two
+                    // vertically adjacent pixels x half of the output channels (fwd_rows2)
     int cg;         // forward, tiles of <= 128 pixels: input-channel groups computing partial sums in parallel
                     // (256 / pixels threads per pixel instead of one busy wave), summed through LDS
     int fuse;       // backward: the fused output-conv launch (forward + loss + backward, gpi_conv_loss_fused)
@@ -204,6 +205,24 @@ constexpr int ZREG = 3;
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return v && *v ? atoi(v) : dflt;
+}
+
+// NPX value of the forward's row-pair form (ConvGeom::npx, ShapeC::npxk): two vertically adjacent output
+// pixels x half of the output channels per thread
+constexpr int NPX_ROWS2 = -2;
+// weight floats per input channel in LDS: [taps][CP], or for the row-pair form [half][taps][HS] with HS = CP / 2
+// rounded up to an even count and each half's block padded to whole 16-byte reads
+__host__ __device__ constexpr int fwd_wci(int kk, int cp, int npx) {
+    return npx == NPX_ROWS2 ? 2 * ((kk * ((cp / 2 + 1) & ~1) + 3) & ~3) : kk * cp;
+}
+// the forward launches that take it: 3x3 / stride-1 (also upsampling) tiles of exactly 256 pixels on 16- and
+// 32-wide planes (16 or 8 rows: full and half tiles both pair rows, and the statistics epilogue reproduces the
+// one-pixel form's order of additions for these two widths), 3 to 8 output channels with the statistics or
+// plain epilogue.  Not the 4-row tiles of 64-wide planes: DecBlock4.dl2.fwd of the 256^2 configuration (11 -> 4)
+// measured 20.5 -> 29.7 us with it (profiles/r07_ab_fwd_rows2.txt)
+bool fwd_rows2(const gpi_conv_desc& d, const ConvGeom& G) {
+    return d.k == 3 && d.stride == 1 && d.cout >= 3 && d.cout <= 8 && G.th * d.w_out == 256 &&
+           (d.w_out == 16 || d.w_out == 32) && d.epilogue != GPI_EPI_GAUSS_LOSS && d.epilogue != GPI_EPI_GAUSS_EXP_LOSS;
 }
 
 
@@ -308,6 +327,13 @@ bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fw
         static const int cg_on = env_int("GPI_FWD_CG", 1);
         const int tp = G.th * d.w_out;
         if (cg_on && tp <= 128 && 256 % tp == 0 && !d.upsample && d.k <= 3) G.cg = std::min(256 / tp, d.cin);
+    }
+    // the forward's row-pair form where fwd_rows2 holds: a predicate on the descriptor and the geometry alone,
+    // so a launch's generic and compile-time shape kernels take the same form.  GPI_FWD_ROWS2=0 keeps the
+    // one-pixel form (A/B runs, tests/test_gpu_conv_blocking.py)
+    if (fwd && G.npx == 1 && G.cg == 1) {
+        static const int rows2 = env_int("GPI_FWD_ROWS2", 1);
+        if (rows2 && fwd_rows2(d, G)) G.npx = NPX_ROWS2;
     }
     // the BN-backward operand image in registers when it is small: LDS = gradient + input images only
     // (one more resident workgroup per CU on the 32x32 / 64x64 decoder planes)
@@ -891,8 +917,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
     float* scratch = sh + GPI_MAX_CIN;   // 2*CP*4 <= 64
     float* red = scratch + 64;           // 2*CP <= 16
     float* dsl = red + 16;               // [CP] Dropout2d scales of this sample's output channels
-    float* wT = smem + pad256(FWD_HDR);  // [cin][KK][CP]
-    const int nw = d.cin * KK * CP;
+    // row-pair form: HC accumulator channels per thread and pixel, HS weight slots per tap of a channel half,
+    // WH floats per (input channel, half)
+    constexpr bool ROWS2 = NPX == NPX_ROWS2;
+    constexpr int WCI = fwd_wci(KK, CP, NPX), HC = CP / 2, HS = (HC + 1) & ~1, WH = (KK * HS + 3) & ~3;
+    static_assert(!ROWS2 || (K == 3 && S == 1 && WCI == 2 * WH), "the row-pair form is the 3x3 / stride-1 forward's");
+    float* wT = smem + pad256(FWD_HDR);  // [cin][KK][CP]; row pairs: [cin][2][KK][HS] (fwd_wci)
+    const int nw = d.cin * WCI;
     float* img = wT + pad256(nw);        // [cin][rh][P] + zero margin
 
     const int tid = threadIdx.x;
@@ -912,6 +943,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
 
     // ---- phase 1: every global read of the tile in flight together
     stage(wT, nw, zero, [&](int e) -> const float* {
+        if constexpr (ROWS2) {
+            // slot (half, tap, j) holds channel half * ceil(cout / 2) + j: halves of ceil(cout / 2) and
+            // floor(cout / 2) channels; the other slots and the padding hold zeros
+            const int ci = e / WCI, q = e - ci * WCI, hf = q / WH, i = q - hf * WH, tap = i / HS, j = i - tap * HS;
+            const int c2 = (d.cout + 1) >> 1;
+            const bool ok = tap < KK && j < (hf ? d.cout - c2 : c2);
+            return ok ? params + w_off + ((int64_t)(hf * c2 + j) * d.cin + ci) * KK + tap : nullptr;
+        }
         const int co = e % CP, r = e / CP;
         return co < d.cout ? params + w_off + (int64_t)co * d.cin * KK + r : nullptr;
     });
@@ -953,7 +992,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
     // ---- phase 4: compute.  NPX == 1: one output pixel per thread and pass (two passes only for the
     // 256-wide upsampled planes, whose tiles pair output rows).  NPX > 1: NPX horizontally adjacent
     // pixels per thread; per (ci, ky) the thread reads the input row window the NPX x K taps cover
-    // once into registers, and every weight vector read serves NPX pixels.
+    // once into registers, and every weight vector read serves NPX pixels.  NPX_ROWS2: the pixels (oy, ox)
+    // and (oy + 1, ox) x one half of the output channels per thread (see there).
     const int tp = Gt.th * d.w_out;
     float Lv = 0.f;
     float vst[2 * CP];
@@ -1093,6 +1133,156 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
                 }
             }
         }
+    } else if constexpr (ROWS2) {
+        // One pixel per thread reads CP weights (wave-uniform: every lane repeats the broadcast read) and one
+        // window value per tap for CP FMAs -- 2.5 to 3 LDS-array cycles per VALU cycle.  Here threads
+        // [0, 128) and [128, 256) (waves {0, 1} and {2, 3}: the channel half is wave-uniform) each take the
+        // tile's 128 vertical pixel pairs and one half of the output channels: a weight read is half as wide
+        // and serves two pixels, and the pair's 4 x 3 window (3 x 2 source values when upsampling) is read
+        // once per input channel by conflict-free single-dword reads (lanes along a row; a horizontal pair's
+        // window starts at an odd dword and its lanes stride two banks).  Every output accumulates over
+        // (ci, ky, kx) as in the one-pixel form and the statistics are summed in its order of additions (below):
+        // stored values and statistics keep their bits.
+        const int hf = tid >> 7, g = tid & 127;
+        const int c2 = (d.cout + 1) >> 1;            // channels of half 0; half 1 has the rest
+        const int nh = hf ? d.cout - c2 : c2, c0 = hf * c2;
+        const int py = dq(g, Gt.d_wout), ox = g - py * d.w_out;
+        const int ty = 2 * py, oy = T.oy0 + ty;
+        const bool active = 2 * g < tp;
+        PHASE(5);
+        float acc[2][HC];
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int j = 0; j < HC; ++j) acc[p][j] = 0.f;
+        if (active && !SKIP(G, 64)) {
+            constexpr int NR = UP ? 3 : 4;           // source rows under the pair's taps
+            const int plane = Gt.rh * Gt.P;
+            const int r0 = UP ? fdiv2(oy - 1) - iy0 : ty;
+            const int cb = (UP ? fdiv2(ox - 1) : ox - 1) + HALO;
+            const float* t0 = img + r0 * Gt.P + cb;
+            // (one input channel per iteration also with a compile-time cin: fully unrolled, the scheduler hoisted
+            // the reads of several channels and two of the shape instantiations spilled at the 5-wave budget)
+#pragma unroll 1
+            for (int ci = 0; ci < d.cin; ++ci) {
+                const float* tci = t0 + ci * plane;
+                int wofs = pad256(FWD_HDR) + ci * WCI + hf * WH;   // (a VGPR base: see the one-pixel form)
+                if (GPI_FWD_WVGPR) asm volatile("" : "+v"(wofs));
+                // the half's weights of this input channel by whole 16-byte reads (ds_read_b128: 4 LDS cycles
+                // per 16 B, the rate of ds_read_b64).  The four floats pass one empty asm (not volatile: no
+                // scheduling barrier) so that the compiler keeps the reads whole: it narrowed the reads of a
+                // 3-channel half to ds_read_b96 (8 cycles) and paired 8-byte reads into ds_read2_b64 (8 cycles
+                // for 16 B)
+                float wv[WH];
+#pragma unroll
+                for (int q = 0; q < WH / 4; ++q) {
+                    // (the alignment stated: behind the opaque offset the compiler assumed 4 bytes and split the read)
+                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(smem + wofs + 4 * q, 16));
+                    float w0 = w4[0], w1 = w4[1], w2 = w4[2], w3 = w4[3];
+                    asm("" : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3));
+                    wv[4 * q] = w0, wv[4 * q + 1] = w1, wv[4 * q + 2] = w2, wv[4 * q + 3] = w3;
+                }
+                float win[NR][K];
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const float* trow = tci + r * Gt.P;
+                    if constexpr (UP) {
+                        // columns floor((ox - 1 + kx) / 2): two source values, the middle tap by the parity of ox
+                        const float v0 = trow[0], v1 = trow[1];
+                        win[r][0] = v0;
+                        win[r][1] = (ox & 1) ? v0 : v1;
+                        win[r][2] = v1;
+                    } else {
+#pragma unroll
+                        for (int kx = 0; kx < K; ++kx) win[r][kx] = trow[kx];
+                    }
+                }
+#pragma unroll
+                for (int ky = 0; ky < K; ++ky) {
+#pragma unroll
+                    for (int kx = 0; kx < K; ++kx) {
+#pragma unroll
+                        for (int p = 0; p < 2; ++p) {
+                            // source row of output row oy + p, tap ky (oy is even): floor((oy + p - 1 + ky) / 2)
+                            const float v = win[UP ? ((p + ky + 1) >> 1) : p + ky][kx];
+#pragma unroll
+                            for (int j = 0; j < HC; ++j) acc[p][j] = fmaf(wv[(ky * K + kx) * HS + j], v, acc[p][j]);
+                        }
+                    }
+                }
+            }
+        }
+        PHASE(6);
+        // (j < c2 folds the padded accumulators of a compile-time shape away; j < nh is the half's own count)
+        if (drop) {
+#pragma unroll
+            for (int j = 0; j < HC; ++j) {
+                if (j < c2 && j < nh) {
+                    const float ds = dsl[c0 + j];
+                    acc[0][j] *= ds;
+                    acc[1][j] *= ds;
+                }
+            }
+        }
+        if (active) {
+            float* o = ws + d.out_off + ((int64_t)T.b * d.out_ctot + d.out_c0 + c0) * HWo + oy * d.w_out + ox;
+#pragma unroll
+            for (int j = 0; j < HC; ++j) {
+                if (j < c2 && j < nh) {
+                    st1(o + (int64_t)j * HWo, acc[0][j]);
+                    st1(o + (int64_t)j * HWo + d.w_out, acc[1][j]);
+                }
+            }
+        }
+        if (d.epilogue == GPI_EPI_STORE_STATS && !SKIP(G, 128)) {
+            // The sums in the one-pixel form's order of additions, so that the statistics -- and with them every
+            // later launch of a step -- keep their bits: there wave w holds the tile's pixels [64 w, 64 w + 64),
+            // block_sum's DPP ladder sums each 16-lane row R0..R3 (the same lanes as here), then
+            // (R3 + R2) + (R1 + R0), then the four waves in order.  A wave here holds the upper (s0) and lower
+            // (s1) pixels of 64 pairs = two of those waves: on 32-wide planes rows (R0, R1) are the upper and
+            // (R2, R3) the lower pixels of two rows of lanes, on 16-wide ones (R0, R1) and (R2, R3) are the
+            // (upper, lower) pixels of one row of lanes each.
+            float s0[2 * HC], s1[2 * HC], y[2 * HC];
+#pragma unroll
+            for (int j = 0; j < HC; ++j) {
+                const bool ok = active && j < c2 && j < nh;
+                const float a0 = ok ? acc[0][j] : 0.f, a1 = ok ? acc[1][j] : 0.f;
+                s0[2 * j] = a0, s0[2 * j + 1] = a0 * a0;
+                s1[2 * j] = a1, s1[2 * j + 1] = a1 * a1;
+            }
+            dpp_step<0xb1, 0xf>(s0), dpp_step<0xb1, 0xf>(s1);      // the row sums, as wave_sums
+            dpp_step<0x4e, 0xf>(s0), dpp_step<0x4e, 0xf>(s1);
+            dpp_step<0x124, 0xf>(s0), dpp_step<0x124, 0xf>(s1);
+            dpp_step<0x128, 0xf>(s0), dpp_step<0x128, 0xf>(s1);
+            if (d.w_out == 32) {
+                dpp_step<0x142, 0xa>(s0), dpp_step<0x142, 0xa>(s1);   // row_bcast:15: (R1 + R0), (R3 + R2)
+#pragma unroll
+                for (int q = 0; q < 2 * HC; ++q) y[q] = s1[q] + s0[q];
+            } else {
+#pragma unroll
+                for (int q = 0; q < 2 * HC; ++q) y[q] = s1[q] + s0[q];   // (R1 + R0) and (R3 + R2) per row of lanes
+                dpp_step<0x142, 0xa>(y);
+            }
+            // lanes 31 / 63 hold the sums of the one-pixel form's waves 2 u / 2 u + 1 (u: this wave of its half);
+            // scratch [2 channel + stat][wave], the slots of the half's own channels only
+            const int u = (tid >> 6) & 1;
+#pragma unroll
+            for (int q = 0; q < 2 * HC; ++q) {
+                const float lo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y[q]), 31));
+                const float hi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y[q]), 63));
+                if ((tid & 63) == 0 && (q >> 1) < c2 && (q >> 1) < nh) {
+                    scratch[(2 * c0 + q) * 4 + 2 * u] = lo;
+                    scratch[(2 * c0 + q) * 4 + 2 * u + 1] = hi;
+                }
+            }
+            __syncthreads();
+            if (tid < 2 * d.cout && !SKIP(G, 4)) {
+                float s = 0.f;
+                for (int w = 0; w < 4; ++w) s += scratch[tid * 4 + w];
+                gpi_stat* st = stat_slot(c, d.out_stat + (tid >> 1), T.grp);
+                atomicAdd((tid & 1) ? &st->sumsq : &st->sum, (double)s);
+            }
+        }
     } else {
         // NPX == 0: the channel-group instantiation (Gt.cg > 1), otherwise one group (folds away)
         const int cg = NPX == 0 ? Gt.cg : 1;
@@ -1195,7 +1385,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
         }
     }
 
-    if (d.epilogue == GPI_EPI_GAUSS_LOSS || d.epilogue == GPI_EPI_GAUSS_EXP_LOSS) {
+    if (!ROWS2 && (d.epilogue == GPI_EPI_GAUSS_LOSS || d.epilogue == GPI_EPI_GAUSS_EXP_LOSS)) {   // (fwd_rows2: never)
         float v[1] = {Lv};
         block_sum<1>(v, scratch, red);      // thread 0 wrote red[0] itself: no barrier before reading it
         if (tid == 0 && !SKIP(G, 4)) atomicAdd(c.loss_acc + T.grp * GPI_REPLICAS + blockIdx.x % GPI_REPLICAS, (double)red[0]);
@@ -1203,7 +1393,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
         RTSTAMP(1);
         return;
     }
-    if (d.epilogue == GPI_EPI_STORE_STATS && !SKIP(G, 128)) {
+    // (the row-pair form has summed its statistics above)
+    if (!ROWS2 && d.epilogue == GPI_EPI_STORE_STATS && !SKIP(G, 128)) {
 #if GPI_FWD_WAVE_ATOMICS
         // per-wave sums straight to the fp64 replicas (no LDS stage, no barrier): 4 atomics per (channel, stat)
         // per workgroup instead of 1, the wave's own replica (4 blockIdx + wave)
@@ -2627,7 +2818,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
 }
 
 size_t fwd_lds(const gpi_conv_desc& d, const ConvGeom& G, int cp) {
-    return sizeof(float) * ((size_t)pad256(FWD_HDR) + pad256(d.cin * d.k * d.k * cp) + img_floats(d.cin, G.rh, G.P) +
+    return sizeof(float) * ((size_t)pad256(FWD_HDR) + pad256(d.cin * fwd_wci(d.k * d.k, cp, G.npx)) +
+                            img_floats(d.cin, G.rh, G.P) +
                             (G.cg > 1 ? (size_t)(G.cg - 1) * G.th * d.w_out * cp : 0));
 }
 
@@ -2753,6 +2945,13 @@ conv_kernel_t pick(int cp, bool fwd, int npx, bool half, bool ucls = false) {
         if (!fwd && ucls) return half ? conv_bwd_kernel<3, 1, 0, false, true, true> : conv_bwd_kernel<3, 1, 0, false, false, true>;
     }
     if (!fwd) return half ? conv_bwd_kernel<K, S, UP, false, true> : conv_bwd_kernel<K, S, UP>;
+    if constexpr (K == 3 && S == 1) {   // the row-pair form (fwd_rows2: 3 to 8 output channels)
+        if (npx == NPX_ROWS2) {
+            if (cp == 4) return half ? conv_fwd_kernel<K, S, UP, 4, NPX_ROWS2, true> : conv_fwd_kernel<K, S, UP, 4, NPX_ROWS2>;
+            if (cp == 6) return half ? conv_fwd_kernel<K, S, UP, 6, NPX_ROWS2, true> : conv_fwd_kernel<K, S, UP, 6, NPX_ROWS2>;
+            return half ? conv_fwd_kernel<K, S, UP, 8, NPX_ROWS2, true> : conv_fwd_kernel<K, S, UP, 8, NPX_ROWS2>;
+        }
+    }
     if (npx == 4) return pick_cp<K, S, UP, 4>(cp, half);
     if (npx == 2) return pick_cp<K, S, UP, 2>(cp, half);
     if constexpr (!UP && K <= 3) {   // channel-group instantiation: the small-plane codec convs only

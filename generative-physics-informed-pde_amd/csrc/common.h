@@ -138,4 +138,12 @@ __device__ __forceinline__ float u01(uint32_t x) {   // (0, 1]
     return ((float)(x >> 8) + 1.0f) * (1.0f / 16777216.0f);
 }
 
+// one normal per Philox counter (the per-element draws: gpi_gauss_sample, gpi_vo_moments, gpi_gp_sample,
+// GPI_DRAW_GAUSS)
+__device__ __forceinline__ float normal_at(uint64_t ctr, uint64_t sub, uint64_t seed) {
+    const uint4_ q = philox(ctr, sub, seed);
+    const float u0 = u01(q.x), u1 = u01(q.y);
+    return sqrtf(-2.f * logf(u0)) * cosf(6.2831853071795864f * u1);
+}
+
 }  // namespace gpi

@@ -253,6 +253,9 @@ __global__ __launch_bounds__(256) void draws_kernel(DrawArgs a, const uint64_t* 
     const int64_t q = (int64_t)blk * 256 + threadIdx.x;
     if (it.kind == GPI_DRAW_RANDN) randn_body(q, (float*)it.out, it.n, it.seed, base, it.sub);
     else if (it.kind == GPI_DRAW_DROPOUT) dropout_body(q, (float*)it.out, it.n, it.p, 1.f / (1.f - it.p), it.seed, base, it.sub);
+    else if (it.kind == GPI_DRAW_GAUSS) {      // gauss_sample_kernel's element (rep = 1, no eps): one counter per value
+        if (q < it.n) ((float*)it.out)[q] = fmaf(expf(it.logsigma[q]), normal_at(base + (uint64_t)q, it.sub, it.seed), it.mean[q]);
+    }
     else subset_rank_body(blk, hk, (int32_t*)it.out, (int32_t)it.n, (int32_t)it.k, it.seed, base, it.sub, a.epb);
 }
 
@@ -698,6 +701,9 @@ extern "C" int gpi_draws(const gpi_draw_item* items, int n_items, const uint64_t
         } else if (it.kind == GPI_DRAW_DROPOUT) {
             if (!(it.p >= 0.f && it.p < 1.f)) return GPI_ERR_ARG;
             nb += (int)((((it.n + 3) / 4) + 255) / 256);
+        } else if (it.kind == GPI_DRAW_GAUSS) {
+            if (!it.mean || !it.logsigma) return GPI_ERR_ARG;
+            nb += (int)((it.n + 255) / 256);
         } else if (it.kind == GPI_DRAW_SUBSET) {
             if (it.n <= 0 || it.n > 16384 || it.k < 0 || it.k > it.n || ++n_sub > 1) return GPI_ERR_ARG;
             a.epb = subset_epb((int32_t)it.n);

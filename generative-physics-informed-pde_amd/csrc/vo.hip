@@ -251,12 +251,6 @@ __global__ __launch_bounds__(256) void vo_galerkin_kernel(gpi_vo_galerkin_desc d
 // ---------------------------------------------------------------- MC predictive moments
 constexpr int MOM_CH = 64;   // MC samples staged in LDS per chunk
 
-__device__ __forceinline__ float normal_at(uint64_t ctr, uint64_t sub, uint64_t seed) {
-    const uint4_ q = philox(ctr, sub, seed);
-    const float u0 = u01(q.x), u1 = u01(q.y);
-    return sqrtf(-2.f * logf(u0)) * cosf(6.2831853071795864f * u1);
-}
-
 __global__ __launch_bounds__(256) void vo_moments_kernel(gpi_vo_moments_desc d, FineGrid G) {
     extern __shared__ __attribute__((aligned(16))) float su[];   // [MOM_CH][nn_c]
     const int j = blockIdx.y;

@@ -202,11 +202,12 @@ class RandomFieldDesc(C.Structure):
 
 
 GPI_MAX_DRAWS = 6
-DRAW_RANDN, DRAW_DROPOUT, DRAW_SUBSET = 0, 1, 2
+DRAW_RANDN, DRAW_DROPOUT, DRAW_SUBSET, DRAW_GAUSS = 0, 1, 2, 3
 
 
 class DrawItem(C.Structure):
-    _fields_ = [('kind', i32), ('p', f32), ('out', vp), ('n', i64), ('k', i64), ('sub', u64), ('seed', u64)]
+    _fields_ = [('kind', i32), ('p', f32), ('out', vp), ('n', i64), ('k', i64), ('sub', u64), ('seed', u64),
+                ('mean', vp), ('logsigma', vp)]
 
 
 GPI_MAX_RANKS = 16

@@ -888,10 +888,12 @@ class ElboEngine(object):
             val = val + sv * v
         return val.to(torch.float32)
 
-    def terms(self):
-        """Dictionary of the individual ELBO terms (host sync)."""
-        self._check_rom_written()
-        t = self.ws.terms.cpu()
+    def terms(self, terms=None):
+        """Dictionary of the individual ELBO terms (host sync), from the term accumulators or from a saved
+        copy ``terms`` [N_TERMS * R] (the fused step's, whose epilogue clears the accumulators)."""
+        if terms is None:
+            self._check_rom_written()
+        t = (self.ws.terms if terms is None else terms.view(N_TERMS, R).sum(1)).cpu()
         out = {}
         gi = 0
         if self.B_u > 0:

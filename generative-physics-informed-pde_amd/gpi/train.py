@@ -16,7 +16,26 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from . import vo as gvo
 from .engine import ElboEngine
+
+# Philox sub ids of the virtual-observable targets y ~ N(VO.mean, VO.var) (generative.py:356).  The step's
+# draws use sub0 + {1 subset, 2 eps_z, 3 eps_X, 4 / 5 encoder / decoder Dropout2d, 6 y_vo} with sub0 = 0
+# for the draws made during a step (for the next one) and sub0 = 100 for the constructor's; the redraw of
+# the pending target after a VO update uses VO_REDRAW_SUB, the draws after a hold-off switch sub0 =
+# VO_SWITCH_SUB0 -- all at the step's current Philox offset.
+VO_Y_SUB = 6
+VO_REDRAW_SUB = 206
+VO_SWITCH_SUB0 = 300
+NO_POSTERIOR = 'the virtual observables have no posterior yet: call update_virtual_observables'
+
+
+def vo_buffers(vo):
+    """The persistent fp32 (mean, logsigma) device buffers of a VO ensemble, which its updates write in place
+    (VirtualObservablesEnsemble / EnergyVirtualObservablesEnsemble)."""
+    if hasattr(vo, '_mean32'):
+        return vo._mean32, vo._logsig32
+    return vo.mean32, vo.logsig32
 
 
 def allreduce_shared(flat, group=None):
@@ -47,22 +66,48 @@ class FusedElboStep(object):
     """rank / world: data-parallel position.  Every rank holds the same global unlabeled pool and
     draws the same global permutation (``subset_seed``, shared) of which it takes its B_u-slice
     (SURVEY.md section 8e); labeled samples and their q rows are rank-owned; the
-    reparametrisation noise uses ``seed`` (per rank)."""
+    reparametrisation noise uses ``seed`` (per rank).
+
+    X_vo / F_vo (single process only): the virtual-observable term of model.elbo (generative.py:341-392) in
+    the step -- a third decoder BN group, the q['vo'] rows as the head's second segment and a second ROM
+    launch against targets y ~ N(vo.mean, vo.var), drawn with the step's other noise from the ensemble's
+    persistent fp32 buffers (``vo``: model.VO, either ensemble family).  vo_holdoff: the term's logL_x - KL
+    part only (training.py:411); set_vo_holdoff switches.  update_virtual_observables is the loop's VO
+    update (training.py:407-409)."""
 
     def __init__(self, model, X_pool, B_u, X_s=None, Y=None, F=None, lr=1e-2, betas=(0.9, 0.999), eps=1e-8,
                  seed=0, normalize=False, process_group=None, distributed=False, rank=0, world=1, subset_seed=None,
-                 graph_allreduce=True, sync_bn=False, bn_exchange='collective'):
+                 graph_allreduce=True, sync_bn=False, bn_exchange='collective', X_vo=None, F_vo=None, vo=None,
+                 vo_holdoff=False):
         self.model = model
-        self.flat = model.native_flat()
         self.N_s = 0 if X_s is None else int(X_s.shape[0])
+        self.N_vo = 0 if X_vo is None else int(X_vo.shape[0])
         self.B_u = int(B_u)
         self.rank, self.world = int(rank), int(world)
         assert 0 <= self.rank < self.world
+        if self.N_vo and self.world > 1:
+            # the learnable flux-row precision beta sums over ALL VO samples (update_vo_precision): ranks that
+            # each hold a shard of them would need an exchange of those sums, which does not exist
+            raise ValueError('FusedElboStep: the virtual-observable term (X_vo) runs in a single process only: '
+                             'the VO precision update sums over all VO samples, and no exchange of a per-rank '
+                             "shard's sums exists (world = %d)" % self.world)
+        self.flat = model.native_flat()
+        self.X_vo, self.F_vo = X_vo, F_vo
+        self.vo = None
+        if self.N_vo:
+            self.vo = vo if vo is not None else model.VO
+            if self.vo is None or self.vo is not model.VO:
+                raise ValueError('FusedElboStep: vo must be the ensemble registered with the model (model.VO): '
+                                 'update_virtual_observables updates that one')
+            if self.vo.dtype != torch.float32:
+                raise L.NativeError('FusedElboStep: the VO ensemble must keep fp32 mean / logsigma buffers')
+            self._vo_ptrs = tuple(t.data_ptr() for t in vo_buffers(self.vo))
+        self.normalize = normalize
         if subset_seed is None and self.world > 1 and self.B_u > 0:
             # every rank must draw the SAME global permutation (its B_u-slice of it); the per-rank
             # noise seed would give overlapping / duplicated slices without any error
             raise ValueError('FusedElboStep: world > 1 needs an explicit subset_seed shared by all ranks')
-        self.engine = ElboEngine(model, self.B_u, self.N_s, normalize=normalize)
+        self.engine = self._new_engine(vo_holdoff)
         # SyncBN: every codec call's BN statistics over the union of the ranks' batches (ElboEngine.set_sync_bn);
         # default replica-BN (per-rank batch statistics, no collective in the codec).  Any distributed world
         # size, 1 included: a one-rank NCCL job runs (and captures) the same per-conv collectives as the
@@ -71,6 +116,7 @@ class FusedElboStep(object):
         # or 'peer' (the one-shot exchange through the ranks' IPC-mapped buffers, gpi.peer: one launch per
         # seam, any backend, capturable)
         self.sync_bn = bool(sync_bn) and bool(distributed)
+        self.pg = process_group
         self.bn_exchange = bn_exchange if self.sync_bn else None
         self.handoff_flags = torch.zeros(8, dtype=torch.int32, device=self.flat.P.device)   # [0..3] flags, [4] error
         self._peer = None
@@ -81,8 +127,7 @@ class FusedElboStep(object):
             if bn_exchange == 'peer':
                 from .peer import PeerExchange
                 self._peer = PeerExchange(pg, err=self.handoff_flags[4:5])
-            self.engine.set_sync_bn(lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=pg), self.world,
-                                    exchange=self._peer)
+            self._set_sync_bn(self.engine)
         dev = self.flat.P.device
         self.X_pool = X_pool.contiguous().float() if X_pool is not None else None
         self.X_s, self.Y, self.F = X_s, Y, F
@@ -99,7 +144,6 @@ class FusedElboStep(object):
         self.seed = int(seed)
         self.subset_seed = int(seed if subset_seed is None else subset_seed)
         self.distributed = distributed
-        self.pg = process_group
         # RCCL all-reduce captured inside the step's graph (one replay per step, no host hop between
         # the gradient and the update); host-side between two graphs for gloo
         self.graph_allreduce = bool(graph_allreduce)
@@ -120,8 +164,7 @@ class FusedElboStep(object):
         if self.graph_mode == 'streams' and self.distributed and not (
                 self.graph_allreduce and dist.get_backend(self.pg) == dist.Backend.NCCL):
             self.graph_mode = 'single'
-        my_idx = self.idx[self.rank * self.B_u:(self.rank + 1) * self.B_u] if self.B_u else None
-        self.engine.bind(X_u=self.X_pool, u_index=my_idx, X_s=X_s, Y=Y, F=F)
+        self._bind(self.engine)
         n_pool = self.X_pool.shape[0] if self.X_pool is not None else 0
         if self.B_u and self.n_sub > n_pool:
             raise ValueError('the pool (%d) is smaller than the global armortized batch (%d)' % (n_pool, self.n_sub))
@@ -133,12 +176,67 @@ class FusedElboStep(object):
             self._subset_ws = torch.zeros(nb.value, dtype=torch.uint8, device=dev)
         drop_span = max([(p.drop_numel + 3) // 4 + 1 for p in (self.engine.ep, self.engine.dp)
                          if p is not None and p.drop_numel] or [0])
+        # (the span of the step with the VO term active, whichever variant runs: eps_X over N_s + N_vo rows,
+        # the y_vo Gaussian rows one counter per element, not one per four)
         self.rng_span = max(n_pool, (self.engine.B * self.engine.dz + 3) // 4 + 1,
-                            (self.N_s * self.engine.d_x + 3) // 4 + 1, drop_span)
+                            ((self.N_s + self.N_vo) * self.engine.d_x + 3) // 4 + 1, drop_span,
+                            self.N_vo * self.engine.d_y)
         self.adam.rng_offset = self.rng_off.data_ptr()
         self.adam.rng_advance = self.rng_span
-        ws = self.engine.ws
         self.last_terms = torch.zeros(L.GPI_REPLICAS * 16, dtype=torch.float64, device=dev)
+        # single-process steps: the epilogue and Adam in one launch (gpi_step_epilogue_adam; nothing
+        # runs between the gradient delivery and the update); GPI_FUSED_ADAM=0 keeps two launches
+        self.fuse_adam = not self.distributed and os.environ.get('GPI_FUSED_ADAM', '1') != '0'
+        self._build_epilogue()
+        self.done_ctr = torch.zeros(1, dtype=torch.int32, device=dev)
+        # side-stream hand-offs by device flags (gpi_stream_signal / gpi_stream_wait) instead of graph
+        # events between the streams; GPI_HANDOFF=events keeps the events (A/B)
+        self.handoff = os.environ.get('GPI_HANDOFF', 'flags') if self.graph_mode in ('single', 'streams') \
+            else 'events'
+        if self.graph_mode == 'streams' and self.handoff != 'flags':
+            self.graph_mode = 'single'
+        # 'streams': the side stream is gated per step by this counter (no event between the streams), so
+        # each stream's part of the step is captured as a graph of its own
+        self.side_done = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._probed_stream = None
+        self.unroll = 1
+        self.g_fb_k = self.g_side_k = None
+        self._wire_handoff()
+        # lazy surfacing of that error word without a host sync: an async copy to pinned memory after
+        # a replay, read once its event has completed (at the next step() / run() / check_handoff())
+        self._err_host = torch.zeros(1, dtype=torch.int32, pin_memory=True) if dev.type == 'cuda' else None
+        self._err_ev = None
+        self._err_every = int(os.environ.get('GPI_ERR_CHECK_EVERY', '16'))
+        self._n_steps = 0
+        self._fb_pending = False
+        self.graph = None
+        self._one_draw = os.environ.get('GPI_ONE_DRAW', '1') != '0'
+        # the first step's noise; every step then draws the next step's during its backward
+        self._launch_noise(L.stream_handle(), self.idx, sub0=100)
+
+    # ------------------------------------------------------------------
+    def _new_engine(self, vo_holdoff):
+        if not self.N_vo:
+            return ElboEngine(self.model, self.B_u, self.N_s, normalize=self.normalize)
+        return ElboEngine(self.model, self.B_u, self.N_s, normalize=self.normalize, N_vo=self.N_vo,
+                          vo_holdoff=vo_holdoff)
+
+    def _set_sync_bn(self, engine):
+        pg = self.pg
+        engine.set_sync_bn(lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=pg), self.world,
+                           exchange=self._peer)
+
+    def _bind(self, engine):
+        my_idx = self.idx[self.rank * self.B_u:(self.rank + 1) * self.B_u] if self.B_u else None
+        if self.N_vo:
+            engine.bind(X_u=self.X_pool, u_index=my_idx, X_s=self.X_s, Y=self.Y, F=self.F, X_vo=self.X_vo,
+                        F_vo=self.F_vo)
+        else:
+            engine.bind(X_u=self.X_pool, u_index=my_idx, X_s=self.X_s, Y=self.Y, F=self.F)
+
+    def _build_epilogue(self):
+        """The epilogue descriptors over the current engine's scratch and encoder masks."""
+        ws = self.engine.ws
         self.epi = L.StepEpilogueDesc(gacc=self.flat.gacc.data_ptr(), grad=self.flat.G.data_ptr(), n=self.flat.numel,
                                       flags=L.FINALIZE_ZERO, n_terms=self.last_terms.numel(),
                                       step=self.step_ctr.data_ptr(), scratch=ws.t_scr.data_ptr(),
@@ -155,26 +253,13 @@ class FusedElboStep(object):
             self.epi.drop_seed = self.seed
             self.epi.drop_offset = self.rng_off.data_ptr()
             self.epi.drop_sub = 4
-        # single-process steps: the epilogue and Adam in one launch (gpi_step_epilogue_adam; nothing
-        # runs between the gradient delivery and the update); GPI_FUSED_ADAM=0 keeps two launches
-        self.fuse_adam = not self.distributed and os.environ.get('GPI_FUSED_ADAM', '1') != '0'
         self.epi_adam = L.StepEpilogueDesc.from_buffer_copy(self.epi)
         self.epi_adam.step = None                  # Adam's counter: incremented once by the fused launch
-        self.done_ctr = torch.zeros(1, dtype=torch.int32, device=dev)
-        # side-stream hand-offs by device flags (gpi_stream_signal / gpi_stream_wait) instead of graph
-        # events between the streams; GPI_HANDOFF=events keeps the events (A/B)
-        self.handoff = os.environ.get('GPI_HANDOFF', 'flags') if self.graph_mode in ('single', 'streams') \
-            else 'events'
-        if self.graph_mode == 'streams' and self.handoff != 'flags':
-            self.graph_mode = 'single'
-        # 'streams': the side stream is gated per step by this counter (no event between the streams), so
-        # each stream's part of the step is captured as a graph of its own
-        self.side_done = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._probed_stream = None
-        self.unroll = 1
-        self.g_fb_k = self.g_side_k = None
+
+    def _wire_handoff(self, probe=True):
+        """Flag hand-offs of the current engine (probe: verify the stream pair's hardware queues first)."""
         if self.handoff == 'flags':
-            self._configure_handoff()
+            self._configure_handoff(probe)
             if self.fuse_adam:
                 # the join with the side stream's last reduction inside the fused epilogue + Adam launch
                 self.epi_adam.wait_flag = self.handoff_flags.data_ptr() + 4 * 3
@@ -190,19 +275,18 @@ class FusedElboStep(object):
                 self.epi.wait_err = self.handoff_flags.data_ptr() + 4 * 4
                 self.epi.err_slot = self.flat.err_slot
                 self.adam.skip_if = self.flat.G.data_ptr() + 4 * self.flat.err_slot
-        # lazy surfacing of that error word without a host sync: an async copy to pinned memory after
-        # a replay, read once its event has completed (at the next step() / run() / check_handoff())
-        self._err_host = torch.zeros(1, dtype=torch.int32, pin_memory=True) if dev.type == 'cuda' else None
-        self._err_ev = None
-        self._err_every = int(os.environ.get('GPI_ERR_CHECK_EVERY', '16'))
-        self._n_steps = 0
-        self._fb_pending = False
-        self.graph = None
-        self._one_draw = os.environ.get('GPI_ONE_DRAW', '1') != '0'
-        # the first step's noise; every step then draws the next step's during its backward
-        self._launch_noise(L.stream_handle(), self.idx, sub0=100)
 
-    # ------------------------------------------------------------------
+    def _vo_sources(self):
+        """The VO ensemble's (mean, logsigma) fp32 buffers the y_vo draw reads at launch; raises before a
+        posterior exists and when the ensemble no longer holds the buffers the step was built on."""
+        if self.vo.mean is None:
+            raise RuntimeError(NO_POSTERIOR)
+        mean, ls = vo_buffers(self.vo)
+        if (mean.data_ptr(), ls.data_ptr()) != self._vo_ptrs:
+            raise L.NativeError('FusedElboStep: the VO ensemble replaced its mean / logsigma buffers; the step '
+                                '(and its captured graphs) reads the old ones: rebuild the step')
+        return mean, ls
+
     def _launch_subset(self, st, idx, sub0=0):
         if not self.B_u:
             return
@@ -219,6 +303,8 @@ class FusedElboStep(object):
         buffers.  Philox streams: the step's offset (advanced by Adam at the end of every step)
         and sub ids sub0 + {1, 2, 3}; the noise drawn during step k (for step k+1) therefore
         differs from step k's own, which was drawn during step k-1 or by the prologue (sub0 = 100).
+        With the VO term active also its targets y_vo ~ N(VO.mean, VO.var) (sub id sub0 + 6), read from the
+        ensemble's buffers when the launch runs: a replay draws from the posterior the last update wrote.
         All of it in ONE launch (gpi_draws: the same draws as the separate entry points, bit for bit)
         unless the pool needs the multi-launch subset form or GPI_ONE_DRAW=0."""
         lib = L.lib()
@@ -239,6 +325,11 @@ class FusedElboStep(object):
                 ex = e.eps_x()
                 items.append(L.DrawItem(kind=L.DRAW_RANDN, out=ex.data_ptr(), n=ex.numel(), sub=sub0 + 3,
                                         seed=self.seed))
+            if e.N_vo and not e.vo_holdoff:
+                yv = e.y_vo()
+                mean, ls = self._vo_sources()
+                items.append(L.DrawItem(kind=L.DRAW_GAUSS, out=yv.data_ptr(), n=yv.numel(), sub=sub0 + VO_Y_SUB,
+                                        seed=self.seed, mean=mean.data_ptr(), logsigma=ls.data_ptr()))
             arr = (L.DrawItem * len(items))(*items)
             L.check(lib.gpi_draws(arr, len(items), L.ptr(self.rng_off), st), 'step draws')
             return
@@ -251,6 +342,10 @@ class FusedElboStep(object):
         if self.engine.N_ex:
             ex = self.engine.eps_x()
             L.check(lib.gpi_randn(L.ptr(ex), ex.numel(), self.seed, L.ptr(self.rng_off), sub0 + 3, st), 'randn x')
+        if self.engine.N_vo and not self.engine.vo_holdoff:
+            mean, ls = self._vo_sources()
+            gvo.gauss_sample(self.engine.y_vo(), mean, ls, seed=self.seed, offset=self.rng_off, sub=sub0 + VO_Y_SUB,
+                             stream=st)
 
     def forward_backward(self, stream=None):
         """One step without the parameter update (gradient in flat.G and the ELBO terms delivered;
@@ -441,11 +536,11 @@ class FusedElboStep(object):
             e._side = None          # next candidate
         return False
 
-    def _configure_handoff(self):
+    def _configure_handoff(self, probe=True):
         """Flag hand-offs between the streams; graph mode 'streams' (no event between the streams at all)
         only on a verified pair of hardware queues, else 'single' (one graph whose event fork / join at
         its ends the runtime orders)."""
-        if self.graph_mode == 'streams' and not self._queues_separate():
+        if probe and self.graph_mode == 'streams' and not self._queues_separate():
             self.graph_mode = 'single'
         self.engine.set_flag_handoff(self.handoff_flags[:4], self.step_ctr, self.handoff_flags[4:5],
                                      side_done=self.side_done if self.graph_mode == 'streams' else None)
@@ -628,3 +723,66 @@ class FusedElboStep(object):
     def elbo(self):
         """ELBO value of the last completed step (0-d tensor)."""
         return self.engine.elbo_value(self.last_terms)
+
+    def terms(self):
+        """The individual ELBO terms of the last completed step (ElboEngine.terms; host sync)."""
+        return self.engine.terms(self.last_terms)
+
+    # ------------------------------------------------------------------ virtual observables
+    def _require_vo(self, what):
+        if not self.N_vo:
+            raise L.NativeError('FusedElboStep.%s: the step was built without X_vo' % what)
+        if self._fb_pending:
+            raise RuntimeError('FusedElboStep.%s between forward_backward() and update(): the pending update '
+                               'still reads this step\'s gradient and noise' % what)
+
+    @torch.no_grad()
+    def update_virtual_observables(self, N_monte_carlo, step, eps=None, Resample=True):
+        """The loop's VO update (training.py:407-409) between two steps: model.update_virtual_observables,
+        which writes the ensemble's posterior buffers in place, then a redraw of the pending target y_vo
+        from the new posterior (the next step's was drawn during the previous step's backward from the old
+        one; the reference draws y at elbo() time, after the update).  The redraw runs eagerly at the
+        current Philox offset, sub id VO_REDRAW_SUB.  Ordered by device synchronisation after the previous
+        step's work on both streams and before the next replay (a host-bound ~1 ms call once per update
+        interval); captured graphs stay valid: they read the ensemble's buffers at launch."""
+        self._require_vo('update_virtual_observables')
+        torch.cuda.synchronize()
+        self.model.update_virtual_observables(N_monte_carlo, step=step, eps=eps, Resample=Resample)
+        mean, ls = self._vo_sources()
+        if not self.engine.vo_holdoff:
+            gvo.gauss_sample(self.engine.y_vo(), mean, ls, seed=self.seed, offset=self.rng_off, sub=VO_REDRAW_SUB)
+        torch.cuda.synchronize()
+
+    def set_vo_holdoff(self, flag):
+        """training.py:411's ``gn < N_vo_holdoff`` switch: rebuild the engine for the other variant of the VO
+        term on the same flat parameters and draw that engine's pending noise (masks, eps_z, eps_X, y_vo:
+        sub ids VO_SWITCH_SUB0 + {2 .. 6} at the current Philox offset; the pending subset stays).
+        Parameters, Adam moments, step counter, Philox offset, learning rate, scheduler handle and BN
+        running buffers are untouched.  Captured graphs are dropped: step() runs eagerly until the next
+        capture().  elbo() / terms() of the last step before the switch are to be read before it."""
+        self._require_vo('set_vo_holdoff')
+        flag = bool(flag)
+        if flag == self.engine.vo_holdoff:
+            return
+        if not flag:
+            self._vo_sources()              # (no posterior yet: raise before anything changes)
+        torch.cuda.synchronize()
+        old = self.engine
+        new = self._new_engine(flag)
+        # the stream pair (probed hardware queues) and its events go with the step, not the engine
+        for k in ('_side', '_ev_fork', '_ev_join', '_ev_fork2', '_ev_join2', '_ev_enc', '_ev_start'):
+            if hasattr(old, k):
+                setattr(new, k, getattr(old, k))
+        new.ws.t_flag.copy_(old.ws.t_flag)  # (the ROM's sticky conductivity flag: check_flag)
+        if self.sync_bn:
+            self._set_sync_bn(new)
+        self._bind(new)
+        self.engine = new
+        self._build_epilogue()
+        self._wire_handoff(probe=False)
+        self.graph = None
+        self.g_fb = self.g_up = self.g_side = self.segs = None
+        self.g_fb_k = self.g_side_k = None
+        self.unroll = 1
+        self._launch_noise(L.stream_handle(), self.idx, sub0=VO_SWITCH_SUB0, subset=False)
+        torch.cuda.synchronize()

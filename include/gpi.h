@@ -756,11 +756,16 @@ int gpi_queue_probe(const uint32_t* flag, uint32_t* seen, void* stream);
  * decoder's Dropout2d scales, the random subset, the reparametrisation noise), each item bit-identical to its
  * own entry point's launch with the same seed / offset / sub: GPI_DRAW_RANDN = gpi_randn(out, n, ...),
  * GPI_DRAW_DROPOUT = gpi_dropout_masks(out, n, p, ...), GPI_DRAW_SUBSET = gpi_random_subset(out, n, k, ...)
- * (pool n <= 16384; at most one subset item).  Workgroups are dealt to the items by block ranges. */
+ * (pool n <= 16384; at most one subset item), GPI_DRAW_GAUSS = gpi_gauss_sample(out, mean, logsigma, rows, dim,
+ * rep = 1, eps = NULL, ...) with rows * dim = n: out[e] = fmaf(expf(logsigma[e]), N(0,1), mean[e]), the normal from
+ * Philox counter (*offset + e) -- one counter per value, not one per four as GPI_DRAW_RANDN.  mean / logsigma are
+ * read from device memory when the launch runs, so a replayed graph draws from whatever an in-place update of
+ * them (gpi_vo_condition, gpi_vo_energy) wrote last.  Workgroups are dealt to the items by block ranges. */
 #define GPI_MAX_DRAWS 6
 #define GPI_DRAW_RANDN   0
 #define GPI_DRAW_DROPOUT 1
 #define GPI_DRAW_SUBSET  2
+#define GPI_DRAW_GAUSS   3
 typedef struct gpi_draw_item {
     int32_t kind;
     float p;                   /* dropout probability (GPI_DRAW_DROPOUT) */
@@ -769,6 +774,8 @@ typedef struct gpi_draw_item {
     int64_t k;                 /* subset size */
     uint64_t sub;              /* Philox sub stream */
     uint64_t seed;             /* Philox key (the subset's: the seed shared by every rank) */
+    const float* mean;         /* [n] (GPI_DRAW_GAUSS; NULL otherwise) */
+    const float* logsigma;     /* [n] (GPI_DRAW_GAUSS; NULL otherwise) */
 } gpi_draw_item;
 int gpi_draws(const gpi_draw_item* items, int n_items, const uint64_t* offset, void* stream);
 int gpi_randn(float* out, int64_t n, uint64_t seed, const uint64_t* offset, uint64_t sub, void* stream);

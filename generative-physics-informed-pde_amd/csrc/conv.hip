@@ -99,15 +99,6 @@ __host__ __device__ inline int fdiv2(int x) { return x >= 0 ? x / 2 : -((-x + 1)
 __host__ __device__ inline int cdiv2(int x) { return -fdiv2(-x); }
 __host__ __device__ inline int pad256(int n) { return (n + 255) & ~255; }
 
-// forward statistics epilogue: each wave's sums as fp64 atomics of its own (1) or the workgroup's sum through LDS (0)
-#ifndef GPI_FWD_WAVE_ATOMICS
-#define GPI_FWD_WAVE_ATOMICS 0
-#endif
-// forward (one pixel per thread): the per-channel weight offset forced into a VGPR (1) or left to the compiler (0)
-#ifndef GPI_FWD_WVGPR
-#define GPI_FWD_WVGPR 1
-#endif
-
 // Tile geometry: tile t of sample b covers output rows [t*th, (t+1)*th), all columns.
 struct ConvGeom {
     int th, tiles, nblocks;
@@ -225,6 +216,31 @@ bool fwd_rows2(const gpi_conv_desc& d, const ConvGeom& G) {
            (d.w_out == 16 || d.w_out == 32) && d.epilogue != GPI_EPI_GAUSS_LOSS && d.epilogue != GPI_EPI_GAUSS_EXP_LOSS;
 }
 
+// The per-tile quantities of tiles of th output rows on row images of pitch P (input) and PG (output gradient)
+ConvGeom::Alt tile_geom(const gpi_conv_desc& d, int P, int PG, int th, bool fwd, bool fuse) {
+    ConvGeom::Alt a;
+    int i0;
+    a.th = th;
+    in_rows(d.k, d.stride, d.upsample, d.pad, 0, th, i0, a.rh);
+    if (d.upsample) a.rh += 1;   // parity-independent bound
+    if (fuse) a.rh += d.k - 1;   // fused output conv: the forward's input rows above and below
+    g_rows(d.k, d.stride, d.pad, 0, th, i0, a.gh);
+    owned_rows(d.stride, d.upsample, 0, th, i0, a.ph);
+    // the BN-backward operand image in registers when it is small: LDS = gradient + input images only
+    // (one more resident workgroup per CU on the 32x32 / 64x64 decoder planes)
+    a.zreg = (!fwd && d.gout_mode == 0 && (int64_t)d.cout * a.gh * (PG / 4) <= (int64_t)ZREG * 256) ? 1 : 0;
+    const int P4 = P / 4, pl = a.rh * P4, Q4 = PG / 4, gl = a.gh * Q4;
+    a.in_sq = 256 / pl;
+    a.in_sr = (256 % pl) / P4;
+    a.in_sc = (256 % pl) % P4;
+    a.g_sq = 256 / gl;
+    a.g_sr = (256 % gl) / Q4;
+    a.g_sc = (256 % gl) % Q4;
+    a.d_in4 = mkdiv(pl);
+    a.d_g4 = mkdiv(gl);
+    a.d_tp = mkdiv(th * d.w_out);
+    return a;
+}
 
 bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fwd, bool fuse = false) {
     if (g.n_groups < 1 || g.n_groups > GPI_MAX_GROUPS) return false;
@@ -294,14 +310,15 @@ bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fw
     if (d.upsample && (G.th & 1)) return false;
     G.tiles = d.h_out / G.th;
     G.nblocks = B * G.tiles;
-    int i0;
-    in_rows(d.k, d.stride, d.upsample, d.pad, 0, G.th, i0, G.rh);
-    if (d.upsample) G.rh += 1;   // parity-independent bound
-    if (fuse) G.rh += d.k - 1;   // fused output conv: the forward's input rows above and below
     G.P = d.w_in + 2 * HALO;
-    g_rows(d.k, d.stride, d.pad, 0, G.th, i0, G.gh);
     G.PG = d.w_out + 2 * HALO;
-    owned_rows(d.stride, d.upsample, 0, G.th, i0, G.ph);
+    // the full tile's geometry, also in ha: a launch without half tiles has ha == the full tile
+    G.ha = tile_geom(d, G.P, G.PG, G.th, fwd, fuse);
+    const ConvGeom::Alt& f = G.ha;
+    G.rh = f.rh, G.gh = f.gh, G.ph = f.ph, G.zreg = f.zreg;
+    G.in_sq = f.in_sq, G.in_sr = f.in_sr, G.in_sc = f.in_sc;
+    G.g_sq = f.g_sq, G.g_sr = f.g_sr, G.g_sc = f.g_sc;
+    G.d_in4 = f.d_in4, G.d_g4 = f.d_g4, G.d_tp = f.d_tp;
     // exactness of the magic divisions: largest dividend * divisor < 2^32
     const uint64_t lim = 1ull << 32;
     const uint64_t in4 = (uint64_t)G.rh * G.P / 4, g4 = (uint64_t)G.gh * G.PG / 4;
@@ -335,9 +352,6 @@ bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fw
         static const int rows2 = env_int("GPI_FWD_ROWS2", 1);
         if (rows2 && fwd_rows2(d, G)) G.npx = NPX_ROWS2;
     }
-    // the BN-backward operand image in registers when it is small: LDS = gradient + input images only
-    // (one more resident workgroup per CU on the 32x32 / 64x64 decoder planes)
-    G.zreg = (!fwd && d.gout_mode == 0 && (int64_t)d.cout * G.gh * (G.PG / 4) <= (int64_t)ZREG * 256) ? 1 : 0;
     G.split = 0;   // decided by launch() from the LDS footprint
     G.fuse = fuse ? 1 : 0;
     G.lsum = 0;     // decided by launch() / gpi_conv_blocks from the LDS footprint (lsum_op)
@@ -358,30 +372,16 @@ bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fw
     static const int dbg = env_int("GPI_DBG_SKIP", 0);
     G.dbg = dbg;
 #endif
-    {
-        const int P4 = G.P / 4, pl = G.rh * P4, Q4 = G.PG / 4, gl = G.gh * Q4;
-        G.in_sq = 256 / pl;
-        G.in_sr = (256 % pl) / P4;
-        G.in_sc = (256 % pl) % P4;
-        G.g_sq = 256 / gl;
-        G.g_sr = (256 % gl) / Q4;
-        G.g_sc = (256 % gl) % Q4;
-    }
-    G.d_in4 = mkdiv((int)in4);
     G.d_P4 = mkdiv(G.P / 4);
-    G.d_g4 = mkdiv((int)g4);
     G.d_PG4 = mkdiv(G.PG / 4);
     G.d_cin = mkdiv(d.cin);
     G.d_cout = mkdiv(d.cout);
     G.d_win = mkdiv(d.w_in);
-    G.d_tp = mkdiv(G.th * d.w_out);
     G.d_wout = mkdiv(d.w_out);
     G.d_w2 = mkdiv(d.w_in >= 2 ? d.w_in / 2 : 1);
     G.nfull = G.nblocks;
     G.half_b = B;
     G.htiles = 0;
-    G.ha = ConvGeom::Alt{G.th, G.rh, G.gh, G.ph, G.zreg, G.in_sq, G.in_sr, G.in_sc, G.g_sq, G.g_sr, G.g_sc,
-                         G.d_in4, G.d_g4, G.d_tp};
     // half tiles for the samples past the largest multiple of 256 tiles (GPI_HALF_TILES: 0 off, 1 the loss
     // op's backward only, 2 every backward launch)
     static const int half_tiles = env_int("GPI_HALF_TILES", 2);
@@ -392,33 +392,14 @@ bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fw
     // the c128 step 1.616 vs 1.558 ms with every launch split)
     if (half_tiles && (fwd ? half_fwd && half_tiles > 1 && G.cg == 1 : (half_tiles > 1 || loss_bwd)) &&
         (G.th & 1) == 0 && base > 0 && tot != base && tot <= 5 * 256 && base % G.tiles == 0) {
-        ConvGeom::Alt& a = G.ha;
-        a.th = G.th / 2;
-        int y0;
-        in_rows(d.k, d.stride, d.upsample, d.pad, 0, a.th, y0, a.rh);
-        if (d.upsample) a.rh += 1;
-        if (fuse) a.rh += d.k - 1;
-        g_rows(d.k, d.stride, d.pad, 0, a.th, y0, a.gh);
-        owned_rows(d.stride, d.upsample, 0, a.th, y0, a.ph);
-        a.zreg = (!fwd && d.gout_mode == 0 && (int64_t)d.cout * a.gh * (G.PG / 4) <= (int64_t)ZREG * 256) ? 1 : 0;
-        const int P4 = G.P / 4, pl = a.rh * P4, Q4 = G.PG / 4, gq = a.gh * Q4;
-        a.in_sq = 256 / pl;
-        a.in_sr = (256 % pl) / P4;
-        a.in_sc = (256 % pl) % P4;
-        a.g_sq = 256 / gq;
-        a.g_sr = (256 % gq) / Q4;
-        a.g_sc = (256 % gq) % Q4;
-        a.d_in4 = mkdiv(pl);
-        a.d_g4 = mkdiv(gq);
-        a.d_tp = mkdiv(a.th * d.w_out);
-        const bool ok = d.gin_off < 0 || (((a.ph * d.w_in) & 15) == 0 && (d.stride != 2 || (a.ph & 1) == 0));
-        if (!ok) a = ConvGeom::Alt{G.th, G.rh, G.gh, G.ph, G.zreg, G.in_sq, G.in_sr, G.in_sc, G.g_sq, G.g_sr, G.g_sc,
-                                   G.d_in4, G.d_g4, G.d_tp};
-        else {
-        G.half_b = base / G.tiles;
-        G.nfull = base;
-        G.htiles = 2 * G.tiles;
-        G.nblocks = base + (B - G.half_b) * G.htiles;
+        const ConvGeom::Alt a = tile_geom(d, G.P, G.PG, G.th / 2, fwd, fuse);
+        // (only where a half tile's owned rows keep the input gradient's 16-pixel blocks and stride-2 row pairs)
+        if (d.gin_off < 0 || (((a.ph * d.w_in) & 15) == 0 && (d.stride != 2 || (a.ph & 1) == 0))) {
+            G.ha = a;
+            G.half_b = base / G.tiles;
+            G.nfull = base;
+            G.htiles = 2 * G.tiles;
+            G.nblocks = base + (B - G.half_b) * G.htiles;
         }
     }
     return true;
@@ -444,7 +425,7 @@ bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fw
 
 struct ShapeC {
     // kernel variant: template arguments of the instantiation, and the signs of the offsets that switch work
-    int fwd, fusek, half, exf, v3, cp, npxk, upk, has_gin, drop, wout, ext_in;
+    int fwd, fusek, half, exf, cp, npxk, upk, has_gin, drop, wout, ext_in;
 #define F(n) int D_##n;
     SHAPE_D(F)
 #undef F
@@ -486,13 +467,11 @@ constexpr int kBounds[5] = GPI_CONV_SHAPE_BOUNDS;
 #endif
 
 // the fused output conv's shape instantiation: which field groups it folds (bit 0 descriptor, 1 geometry,
-// 2 magic divisors); 0: none, the launch keeps the generic kernel.  Its 5-wave budget is at 95 VGPRs already:
+// 2 magic divisors).  Its 5-wave budget is at 95 VGPRs already:
 // with the descriptor folded as well the loss phase unrolls and spills (173 registers; 2-11 for the single
 // groups under hipcc's default contraction), geometry + divisors fit (92 VGPRs) and cut the prologue from
 // 1448 to 933 instructions (620 -> 371 VALU)
-#ifndef GPI_FUSE_FOLD
-#define GPI_FUSE_FOLD 6
-#endif
+constexpr int GPI_FUSE_FOLD = 6;
 
 // the launch's descriptor and geometry with the entry's constants (SHP >= 0; the host matched every field)
 template <int SHP>
@@ -557,11 +536,6 @@ __device__ __forceinline__ void stage(float* dst, int total, const float* zero, 
 // Chunk (16 B) e of a row image of planes of nr rows x P4 chunks decomposed as
 // (plane q, row r, chunk c4), advanced by 256 chunks per step with constant carries
 // (sq, sr, sc) = decomposition of 256, so a loop pays no division per chunk.
-// GPI_STAGE_SEL: the row-image staging loops take each chunk's source by a select of the computed plane address
-// and the zero page (0: the compiler's branchy form, A/B)
-#ifndef GPI_STAGE_SEL
-#define GPI_STAGE_SEL 1
-#endif
 struct ChunkIter {
     int q, r, c4;
     __device__ __forceinline__ void init(int e, int plane4, int P4, Div d_q4, Div d_p4) {
@@ -599,16 +573,12 @@ __device__ __forceinline__ void stage_img(float* dst, int nq, int nr, int P, Div
         if (e0 + wb < total) {
             const int row = r0 + it.r;
             const bool ok = it.q < nq && row >= 0 && row < h && it.c4 >= c4lo && it.c4 < c4hi;
-#if GPI_STAGE_SEL
             // the chunk's plane address computed for every lane (never dereferenced where !ok), then ONE select:
             // without the empty asm the compiler sank the address arithmetic under three exec-masked branches
             // (the bounds tests), ≈ 10 SALU + branch issue per chunk in the staging loops of every conv launch
             const float* pv = plane(it.q) + row * w + 4 * (it.c4 - c4lo);
             asm volatile("" : "+v"(pv));
             const float* p = ok ? pv : zero;
-#else
-            const float* p = ok ? plane(it.q) + row * w + 4 * (it.c4 - c4lo) : zero;
-#endif
             glds16(p, dst + 4 * (e0 + wb));
         }
         it.step(sq, sr, sc, P4, nr);
@@ -746,6 +716,15 @@ __device__ __forceinline__ __attribute__((address_space(1))) T* as_gst(T* p) {
     return (__attribute__((address_space(1))) T*)p;
 }
 
+// G with the per-tile fields of its half-height tiles (kernels of launches with half tiles, GPI_HALF_TILES)
+__device__ __forceinline__ void set_half_tile(ConvGeom& G) {
+    const ConvGeom::Alt& a = G.ha;
+    G.th = a.th; G.rh = a.rh; G.gh = a.gh; G.ph = a.ph; G.zreg = a.zreg;
+    G.in_sq = a.in_sq; G.in_sr = a.in_sr; G.in_sc = a.in_sc;
+    G.g_sq = a.g_sq; G.g_sr = a.g_sr; G.g_sc = a.g_sc;
+    G.d_in4 = a.d_in4; G.d_g4 = a.d_g4; G.d_tp = a.d_tp;
+}
+
 struct TileIdx {
     int b, oy0, grp, gsz;
 };
@@ -845,10 +824,8 @@ __device__ __forceinline__ void lds_window(const float* p, float (&win)[NW]) {
 // Activation / gradient stores of the conv epilogues: write-through (sc1) stores, which leave no dirty
 // line in the XCD's L2 for the kernel-end release to write back (the next launch reads them from memory
 // either way: other XCDs' L2s never see this one's lines).  C64 step 0.6267 vs 0.6346 ms with plain
-// stores (r02 A/B, 3 x 300 replays each; 0.630 vs 0.633 on a second box); GPI_PLAIN_STORES builds the
-// plain form for A/B runs.  The weight-gradient slab partials (scattered dwords) stay plain: write-through
-// measured slower there (0.636-0.652 ms).
-#ifndef GPI_PLAIN_STORES
+// stores (r02 A/B, 3 x 300 replays each; 0.630 vs 0.633 on a second box).  The weight-gradient slab partials
+// (scattered dwords) stay plain: write-through measured slower there (0.636-0.652 ms).
 // relaxed agent-scope atomic stores lower to global_store_dword[x2] sc1 (the compiler schedules and
 // allocates them like ordinary stores)
 // (global address space: a generic pointer would make them flat stores, which also count against the LDS
@@ -867,11 +844,6 @@ __device__ __forceinline__ void st4(float* p, f32x4 v) {
 __device__ __forceinline__ void st1(float* p, float v) {
     __hip_atomic_store((__attribute__((address_space(1))) float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-#else
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *as_gst((f32x4*)p) = v; }
-__device__ __forceinline__ void st2(float* p, f32x2 v) { *as_gst((f32x2*)p) = v; }
-__device__ __forceinline__ void st1(float* p, float v) { *as_gst(p) = v; }
-#endif
 
 // NPX consecutive floats of one output row (16-B / 8-B aligned: x0 is a multiple of NPX, planes are
 // multiples of 4 floats, buffers 16-B aligned -- aligned_ok)
@@ -902,11 +874,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
     ConvGeom Gt_;
     if constexpr (HALF) {
         Gt_ = G;
-        if (logical_block(G) >= G.nfull) {
-            const ConvGeom::Alt& a = G.ha;
-            Gt_.th = a.th; Gt_.rh = a.rh; Gt_.in_sq = a.in_sq; Gt_.in_sr = a.in_sr; Gt_.in_sc = a.in_sc;
-            Gt_.d_in4 = a.d_in4; Gt_.d_tp = a.d_tp;
-        }
+        if (logical_block(G) >= G.nfull) set_half_tile(Gt_);   // (the forward reads the input-side fields only)
     }
     const ConvGeom& Gt = HALF ? Gt_ : G;
     constexpr int KK = K * K;
@@ -1167,7 +1135,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
             for (int ci = 0; ci < d.cin; ++ci) {
                 const float* tci = t0 + ci * plane;
                 int wofs = pad256(FWD_HDR) + ci * WCI + hf * WH;   // (a VGPR base: see the one-pixel form)
-                if (GPI_FWD_WVGPR) asm volatile("" : "+v"(wofs));
+                asm volatile("" : "+v"(wofs));
                 // the half's weights of this input channel by whole 16-byte reads (ds_read_b128: 4 LDS cycles
                 // per 16 B, the rate of ds_read_b64).  The four floats pass one empty asm (not volatile: no
                 // scheduling barrier) so that the compiler keeps the reads whole: it narrowed the reads of a
@@ -1310,7 +1278,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
                     // the weight offset held in a VGPR: the uniform LDS reads then take one VGPR base with
                     // immediate offsets (as an SGPR address every read needed its own v_mov of the address)
                     int wofs = pad256(FWD_HDR) + ci * KK * CP;      // wT = smem + pad256(FWD_HDR)
-                    if (GPI_FWD_WVGPR) asm volatile("" : "+v"(wofs));
+                    asm volatile("" : "+v"(wofs));
                     const float* wci = smem + wofs;
     #pragma unroll
                     for (int ky = 0; ky < K; ++ky) {
@@ -1395,26 +1363,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
     }
     // (the row-pair form has summed its statistics above)
     if (!ROWS2 && d.epilogue == GPI_EPI_STORE_STATS && !SKIP(G, 128)) {
-#if GPI_FWD_WAVE_ATOMICS
-        // per-wave sums straight to the fp64 replicas (no LDS stage, no barrier): 4 atomics per (channel, stat)
-        // per workgroup instead of 1, the wave's own replica (4 blockIdx + wave)
-        wave_sums(vst);
-        const int lane = tid & 63;
-        if (lane < 2 * d.cout && !SKIP(G, 4)) {
-            float v = vst[0];
-#pragma unroll
-            for (int q = 1; q < 2 * CP; ++q) v = lane == q ? vst[q] : v;
-            gpi_stat* st = c.stats + ((int64_t)((4 * blockIdx.x + (tid >> 6)) % GPI_REPLICAS) * GPI_MAX_GROUPS + T.grp) *
-                                         c.n_stats + d.out_stat + (lane >> 1);
-            atomicAdd((lane & 1) ? &st->sumsq : &st->sum, (double)v);
-        }
-#else
         block_sum<2 * CP>(vst, scratch, red);   // thread t < 2 CP wrote red[t] itself: no barrier
         if (tid < 2 * d.cout && !SKIP(G, 4)) {
             gpi_stat* st = stat_slot(c, d.out_stat + (tid >> 1), T.grp);
             atomicAdd((tid & 1) ? &st->sumsq : &st->sum, (double)red[tid]);
         }
-#endif
     }
     PHASE(7);
     RTSTAMP(1);
@@ -1458,41 +1411,9 @@ struct IntC {
     static constexpr int value = V;
 };
 
-// GPI_IG_PRE: the MFMA input gradient's accumulated S_in operands of the second pixel round (tiles of > 256
-// owned pixels) are loaded in phase 1 with the first round's, instead of at the round's start (a global
-// round trip inside the compute phase)
-#ifndef GPI_IG_PRE
-#define GPI_IG_PRE 0
-#endif
-// GPI_S2_IG_SERIAL: the stride-2 input gradient's reduction one MFMA step at a time (table read -> gathered
-// gradient read -> MFMA, the form before r05; A/B only).  Default: four steps' operands in flight per MFMA group
-// GPI_IG_PAIR: the stride-1 / upsampling MFMA input gradient by pixel-block pairs (m, m + 4) sharing the
-// offset-table and weight reads (A/B)
-#ifndef GPI_IG_PAIR
-#define GPI_IG_PAIR 0
-#endif
-#ifndef GPI_S2_IG_SERIAL
-#define GPI_S2_IG_SERIAL 0
-#endif
-// GPI_VDG3: the input gradient of the 3x3 / stride-1 backwards on the VALU (v_pk_fma_f32 over input-channel
-// pairs, the weights by broadcast LDS reads, as the fused output conv's) instead of the MFMA gather form
-// (16 x 16 x 4 blocks, N = cin padded to 16, two dependent LDS reads per step).  Measured r05 (phase probe,
-// tools/phase_probe.py): EncBlock1.dl1.bwd phase 6 18.3 k -> 13.8 k cycles, DecBlock3.dl1 23.1 k -> 20.2 k,
-// launch time -1.0 / -1.3 us (kprof), but the step 0.5591-0.5608 vs 0.5538-0.5544 ms with it off
-// (profiles/r05i_ab_vdg3.txt): off by default; cin 10 (LastTransUp.conv1) was slower still (weight reads)
-#ifndef GPI_VDG3
-#define GPI_VDG3 0
-#endif
 // occupancy target (waves per SIMD) of the 1x1 / 3x3 / 7x7 backward instantiations (no C64 backward launch
 // holds more than 5 workgroups per CU; 4 / 5 / 6 measured alike, r04r)
-#ifndef GPI_BWD_WAVES
-#define GPI_BWD_WAVES 6
-#endif
-// ... of the 3x3 / stride-1 instantiation with the VALU input gradient (its per-thread channel sums and
-// accumulators: 12 spilled VGPRs at 5 waves, none at 4; its launches hold <= 5 workgroups per CU)
-#ifndef GPI_BWD3_WAVES
-#define GPI_BWD3_WAVES 4
-#endif
+constexpr int GPI_BWD_WAVES = 6;
 // per-wave input-channel sums [2][4 waves][32] (256 floats) alias the offset table (>= 256 floats)
 constexpr int SLAB_ROWS = 4;    // partial-slab rows per workgroup: one per wave (no cross-wave dW reduction;
                                 // vop ops: summed in LDS, one row per workgroup)
@@ -1506,31 +1427,14 @@ __host__ __device__ inline int vop_mid_floats(int gh, int w_out, int rowlen, boo
 // forward first -- output rows [oy0 - K/2, oy0 + th + K/2) from an input image K/2 rows taller on each
 // side, the log-likelihood of its owned rows and the loss gradient straight into the LDS gradient
 // image -- then runs the backward on it: no output-gradient round trip through HBM, one launch less.
-#ifndef GPI_FUSE_WAVES
-#define GPI_FUSE_WAVES 5
-#endif
+// Its occupancy target (waves per SIMD):
+constexpr int GPI_FUSE_WAVES = 5;
 // ... of its compile-time shape instantiation (geometry folded: 80 VGPRs fit 6 waves without spills, where the
 // generic kernel spills 14-15)
-#ifndef GPI_FUSE_SHP_WAVES
-#define GPI_FUSE_SHP_WAVES 5
-#endif
-// fused output conv forward: which of the K weight-pair taps come by broadcast LDS read (one ds_read_b64 of
-// the (co 0, co 1) pair) instead of two v_readlane (GPI_FUSE_WLDS = how many; the odd taps first).  The
-// launch: 30.29 / 30.52 us with every pair by readlane, 29.63 / 29.55 with 4 of 5 by LDS, 29.40 / 29.44 with
-// all 5 (r03 A/B): the forward phase was VALU-issue bound, the LDS pipe has room for the broadcast reads
-#ifndef GPI_FUSE_WLDS
-#define GPI_FUSE_WLDS 5
-#endif
-// the VALU input gradient (vop ops): weight channel pairs by broadcast LDS read (1) or v_readlane (0)
-#ifndef GPI_VDG_WLDS
-#define GPI_VDG_WLDS 1
-#endif
-__host__ __device__ constexpr bool fuse_wlds(int ky) {
-    return GPI_FUSE_WLDS <= 0 ? false : (GPI_FUSE_WLDS >= 5 ? true : (ky & 1 ? (ky / 2) < GPI_FUSE_WLDS : (ky / 2) < GPI_FUSE_WLDS - 2));
-}
+constexpr int GPI_FUSE_SHP_WAVES = 5;
 
-template <int K, int S, int UP, bool FUSE = false, bool HALF = false, bool V3 = false, bool EXF = false, int SHP = -1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (FUSE ? (SHP >= 0 ? GPI_FUSE_SHP_WAVES : GPI_FUSE_WAVES) : 4) : (V3 ? GPI_BWD3_WAVES : GPI_BWD_WAVES)))) void conv_bwd_kernel(gpi_conv_desc d, gpi_codec_ctx c, ConvGeom G) {
+template <int K, int S, int UP, bool FUSE = false, bool HALF = false, bool EXF = false, int SHP = -1>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (FUSE ? (SHP >= 0 ? GPI_FUSE_SHP_WAVES : GPI_FUSE_WAVES) : 4) : GPI_BWD_WAVES))) void conv_bwd_kernel(gpi_conv_desc d, gpi_codec_ctx c, ConvGeom G) {
     fold_shape<SHP>(d, G);
     touch_kernargs<CONV_KARG_BYTES>();
     entry_signal(G);
@@ -1545,13 +1449,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
         // prologue ~130 instructions and 7 more argument-load waits, which the launches without half tiles,
         // e.g. the encoder's, do not pay)
         Gt_ = G;
-        if (tile0 >= G.nfull) {
-            const ConvGeom::Alt& a = G.ha;
-            Gt_.th = a.th; Gt_.rh = a.rh; Gt_.gh = a.gh; Gt_.ph = a.ph; Gt_.zreg = a.zreg;
-            Gt_.in_sq = a.in_sq; Gt_.in_sr = a.in_sr; Gt_.in_sc = a.in_sc;
-            Gt_.g_sq = a.g_sq; Gt_.g_sr = a.g_sr; Gt_.g_sc = a.g_sc;
-            Gt_.d_in4 = a.d_in4; Gt_.d_g4 = a.d_g4; Gt_.d_tp = a.d_tp;
-        }
+        if (tile0 >= G.nfull) set_half_tile(Gt_);
     }
     const ConvGeom& Gt = HALF ? Gt_ : G;
     constexpr int KK = K * K;
@@ -1574,12 +1472,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
     // the channel-sum scratch (256) and the four waves' weight-gradient partial rows, summed in LDS
     // into ONE slab row per tile (a quarter of the slab bytes, one coalesced store)
     const bool vop = FUSE || (K == 5 && S == 1 && !UP && has_gin && d.cin <= 4 && d.cout <= 2);
-    // v3: the VALU input gradient of a 3x3 / stride-1 op (GPI_VDG3; tiles of >= 256 owned pixels, cin <= 12):
-    // weights staged as WB3[((co K + ky) K + kx) CIV3 + ci], CIV3 = cin rounded up to 4, in wD's place
-    // (V3: an instantiation of its own -- its accumulators and prefetched operands need a 4-wave VGPR budget,
-    // which the MFMA form's launches of up to 5 workgroups per CU must not pay; picked by v3_op on the host)
-    const bool v3 = V3 && K == 3 && S == 1 && !UP && !FUSE && has_gin && d.cin <= 8 && Gt.ph * d.w_in >= 256;
-    const int CIV3 = (d.cin + 3) & ~3;
     const int J = d.cin * KK;
     const int rowlen = d.cout * J + (d.in_bn ? 2 * d.cin : 0);
     float* wD = smem + bwd_hdr(d.cin, d.cout);        // [KD4][16]: W[co][ci][tap] at (co*KK + tap)*16 + ci, zero padded
@@ -1649,12 +1541,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                 return params + w_off + ((int64_t)co * d.cin + ci) * KK + ky * K + kx;
             });
     }
-    if (has_gin && dg_role && v3)
-        stage(wD, d.cout * KK * CIV3, zero, [&](int e) -> const float* {
-            const int t = e / CIV3, ci = e - t * CIV3, co = t / KK, tap = t - co * KK;
-            return ci < d.cin ? params + w_off + ((int64_t)co * d.cin + ci) * KK + tap : nullptr;
-        });
-    else if (has_gin && dg_role && !vop)
+    if (has_gin && dg_role && !vop)
         stage(wD, nwd, zero, [&](int e) -> const float* {
             const int ci = e & 15, k = e >> 4;
             const int co = k / KK, t = k - co * KK;
@@ -1722,14 +1609,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
     // (FUSE: always the VALU input gradient -- launch() checks cin <= 4 -- so the MFMA input-gradient
     // path and its operand registers compile away)
     const bool vdg = vop && dg_role;     // (launch() never splits a vop op: dg_role holds)
-    const int nmblk = (!FUSE && has_gin && dg_role && !vdg && !v3 && !SKIP(G, 2)) ? (Gt.ph * d.w_in) >> 4 : 0;
+    const int nmblk = (!FUSE && has_gin && dg_role && !vdg && !SKIP(G, 2)) ? (Gt.ph * d.w_in) >> 4 : 0;
     const int ci_l = min(l16, d.cin - 1);
     const bool cok = l16 < d.cin;
     const int64_t ibase = ((int64_t)T.b * d.in_ctot + d.in_c0 + ci_l) * HWi + (int64_t)py0 * d.w_in;
     f32x4 pv4[4];
-#if GPI_IG_PRE
-    f32x4 pv4b[4];            // round 1's operands, loaded with round 0's in phase 1 (GPI_IG_PRE)
-#endif
     auto own_load = [&](int round, f32x4 (&dst)[4]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -1740,28 +1624,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
             else dst[u] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
-    // v3: the previous S_in of this thread's first item (Q = 2 pixels of channels < cin), with the operand loads
-    float pv3[8][2];
-    if (v3 && dg_role && d.gin_accumulate && !SKIP(G, 2)) {
-        const int Q = Gt.ph * d.w_in >= 512 ? 2 : 1;
-        const int gq = tid;
-        const int qy = dq(Q * gq, Gt.d_win), px0 = Q * gq - qy * d.w_in;
-        const bool iok = gq < (Gt.ph * d.w_in) / Q;
-        const int64_t gb_in = ((int64_t)T.b * d.in_ctot + d.in_c0) * HWi + (int64_t)(py0 + qy) * d.w_in + px0;
-#pragma unroll
-        for (int ci = 0; ci < 8; ++ci) {
-            const bool ok = iok && ci < d.cin;
-            const float* pp = ok ? ws + gin_off + gb_in + (int64_t)ci * HWi : zero;
-            pv3[ci][0] = *as_gld(pp);
-            pv3[ci][1] = *as_gld(ok && Q == 2 ? pp + 1 : zero);
-        }
-    }
-    if (nmblk > 0 && S != 2) {
-        own_load(0, pv4);
-#if GPI_IG_PRE
-        if (nmblk > 16) own_load(1, pv4b);
-#endif
-    }
+    if (nmblk > 0 && S != 2) own_load(0, pv4);
     PHASE(9);
     float gam = 0.f, bet = 0.f;
     if (d.in_bn && tid < d.cin) {
@@ -1834,7 +1697,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
             ktab[cls * 2 * KD4 + 2 * k + 1] = 16 * ob;
         }
     }
-    if (has_gin && dg_role && S != 2 && !vop && !v3) {
+    if (has_gin && dg_role && S != 2 && !vop) {
         // A operand of reduction index k = (co, ky, kx) for owned pixel (qy, px):
         // gl[(S1) qy*PG + px | (UP) 2 qy*PG + 2 px] + ktab[k]
         const int ry0 = (UP ? 2 * py0 : py0) + d.pad - gy0;
@@ -1942,15 +1805,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
         // 256 lanes exactly on 64-wide planes (20 rows = 4 groups x 64 columns with 16-row tiles).  Per
         // (ci, kx) the column's RPF + K - 1 input values are read once (lanes on consecutive columns: one
         // 256-B LDS row per read, no bank conflicts) and serve the RPF x K taps.  The weights: a tap's
-        // (co 0, co 1) pair by one broadcast ds_read_b64 (fuse_wlds, the default for every tap) or, for
-        // taps left to the VALU, by two v_readlane from wr[] (lane l holds WF[64 j + l])
+        // (co 0, co 1) pair by one broadcast ds_read_b64 (the forward phase was VALU-issue bound with the pairs
+        // taken by v_readlane; the LDS pipe has room for the broadcast reads)
         const int nrg = (Gt.gh + RPF - 1) / RPF, nitem = nrg * d.w_out;
         auto fwd_items = [&](auto ci_c) {
             constexpr int CIN = decltype(ci_c)::value;
-            constexpr int NWR = (CIN * KK * 2 + 63) / 64;
-            float wr[NWR];
-#pragma unroll
-            for (int j = 0; j < NWR; ++j) wr[j] = mid[256 + 64 * j + lane];
             for (int it = tid; it < nitem; it += 256) {
                 const int rg = dq(it, Gt.d_wout), x = it - rg * d.w_out;
                 const int j0 = rg * RPF;
@@ -1977,15 +1836,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
 #pragma unroll
                         for (int ky = 0; ky < K; ++ky) {
                             const int i = ((ci * K + kx) * K + ky) * 2;
-                            if (fuse_wlds(ky)) {
-                                // (co 0, co 1) pair by one broadcast LDS read: the LDS pipe takes part of
-                                // the weight traffic off the VALU (GPI_FUSE_WLDS taps of K)
-                                w[ky] = *reinterpret_cast<const f32x2*>(mid + 256 + i);
-                            } else {
-                                w[ky][0] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wr[i >> 6]), i & 63));
-                                w[ky][1] = __int_as_float(
-                                    __builtin_amdgcn_readlane(__float_as_int(wr[(i + 1) >> 6]), (i + 1) & 63));
-                            }
+                            w[ky] = *reinterpret_cast<const f32x2*>(mid + 256 + i);
                         }
                         // input row j0 + r feeds pixel p through tap ky = r - p
 #pragma unroll
@@ -2300,20 +2151,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
         }
         const float* arow0 = alb + (ci_l * Gt.rh + (py0 - iy0)) * Gt.P + HALO;   // owned row 0 of channel l16
         const int nkd = KD4 >> 2;
-#if GPI_IG_PAIR
-        bool paired = false;
-        f32x4 acc_next = {0.f, 0.f, 0.f, 0.f};
-#endif
         for (int round = 0; wv + 16 * round < nmblk; ++round) {
-            if (round > 0 && S != 2) {
-#if GPI_IG_PRE
-                if (round == 1) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) pv4[u] = pv4b[u];
-                } else
-#endif
-                own_load(round, pv4);
-            }
+            if (round > 0 && S != 2) own_load(round, pv4);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int m = wv + 4 * (4 * round + u);
@@ -2334,18 +2173,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                         const float* ab = gl + ((py0 >> 1) - gy0 + a2) * Gt.PG + b2 + HALO;
                         const int2* tAB = reinterpret_cast<const int2*>(ktab + cls * 2 * KD4);
                         const int nks = (nk + 3) >> 2;            // (4 nks <= KD4: every table read in range)
-#if GPI_S2_IG_SERIAL
-                        for (int ks = 0; ks < nks; ++ks) {
-                            const int k = 4 * ks + kq;
-                            const int2 t = tAB[k];
-                            const float a = k < nk ? ab[t.x] : 0.f;
-                            acc = mfma4(a, wD[t.y + l16], acc);
-                        }
-#else
-                        // operands of four steps in flight before their MFMAs (the serial form was a chain of two
+                        // operands of four steps in flight before their MFMAs (one step at a time is a chain of two
                         // dependent LDS round trips per MFMA); the padded entries k >= nk hold (0, 0): their
                         // loads stay in range, the select zeroes their A value -- the sums, and their order, are
-                        // the serial form's
+                        // the one-step form's
                         int ks = 0;
                         for (; ks + 4 <= nks; ks += 4) {
                             int2 t[4];
@@ -2366,57 +2197,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                             const float a = ab[t.x], b = wD[t.y + l16];
                             acc = mfma4(k < nk ? a : 0.f, b, acc);
                         }
-#endif
                     } else {
                         const float* gp0 = gl + (UP ? 2 * (qy * Gt.PG + px) : qy * Gt.PG + px);
                         auto aval = [&](int k) -> float {
                             const float* ga = gp0 + ktab[k];
                             return UP ? (ga[0] + ga[1]) + (ga[Gt.PG] + ga[Gt.PG + 1]) : ga[0];
                         };
-#if GPI_IG_PAIR
-                        // block pairs (m, m + 4): one offset-table and weight read per step serve both blocks'
-                        // gathers and MFMAs (two independent accumulator chains); each block's sum and its
-                        // order are the single-block form's
-                        if ((u & 1) && paired) {
-                            acc = acc_next;
-                        } else if (!(u & 1) && m + 4 < nmblk) {
-                            const int i1 = i + 64;
-                            const int qy1 = dq(i1, Gt.d_win), px1 = i1 - qy1 * d.w_in;
-                            const float* gp1 = gl + (UP ? 2 * (qy1 * Gt.PG + px1) : qy1 * Gt.PG + px1);
-                            auto at = [&](const float* ga) -> float {
-                                return UP ? (ga[0] + ga[1]) + (ga[Gt.PG] + ga[Gt.PG + 1]) : ga[0];
-                            };
-                            f32x4 acc1 = {0.f, 0.f, 0.f, 0.f};
-                            int ks = 0;
-                            for (; ks + 4 <= nkd; ks += 4) {
-                                int o[4];
-                                float a0[4], a1[4], b[4];
-#pragma unroll
-                                for (int v = 0; v < 4; ++v) o[v] = ktab[4 * (ks + v) + kq];
-#pragma unroll
-                                for (int v = 0; v < 4; ++v) {
-                                    a0[v] = at(gp0 + o[v]);
-                                    a1[v] = at(gp1 + o[v]);
-                                    b[v] = wD[(4 * (ks + v) + kq) * 16 + l16];
-                                }
-#pragma unroll
-                                for (int v = 0; v < 4; ++v) {
-                                    acc = mfma4(a0[v], b[v], acc);
-                                    acc1 = mfma4(a1[v], b[v], acc1);
-                                }
-                            }
-                            for (; ks < nkd; ++ks) {
-                                const int k = 4 * ks + kq;
-                                const int o = ktab[k];
-                                const float b = wD[k * 16 + l16];
-                                acc = mfma4(at(gp0 + o), b, acc);
-                                acc1 = mfma4(at(gp1 + o), b, acc1);
-                            }
-                            acc_next = acc1;
-                            paired = true;
-                        } else {
-                        paired = false;
-#endif
                         int ks = 0;
                         for (; ks + 4 <= nkd; ks += 4) {   // operands of four steps before their MFMAs
                             float a[4], b[4];
@@ -2433,9 +2219,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                             const int k = 4 * ks + kq;
                             acc = mfma4(aval(k), wD[k * 16 + l16], acc);
                         }
-#if GPI_IG_PAIR
-                        }
-#endif
                     }
                     if (cok && S == 2) {
                         const int nbc = nmblk >> 2, cls = m / nbc, mb = m - cls * nbc;
@@ -2483,122 +2266,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
             }
         }
     }
-#if GPI_VDG3
-    // ---- phase 4b (v3): the 3x3 / stride-1 input gradient on the VALU.  Q consecutive pixels of an owned
-    // row per thread (2 when the tile has >= 512 owned pixels, else 1), all input channels as packed pairs:
-    // per (co, ky) the output-gradient window of the Q pixels (Q + 2 values) from the LDS image, per tap the
-    // CIV3 weights by CIV3 / 4 broadcast ds_read_b128, then Q x CIV3 / 2 v_pk_fma_f32.  The previous S_in
-    // (accumulating ops) is loaded at the item's start, under the compute.  Epilogue as the MFMA form's: ReLU
-    // mask, BN-backward sums, S_in (+)= gamma * dbn; the per-channel sums are wave-summed (DPP) and handed
-    // to the MFMA form's reduction as the kq = 0 lanes' values of channel l16.
-    if constexpr (K == 3 && S == 1 && !UP && !FUSE) {
-        if (v3 && dg_role && !SKIP(G, 2)) {
-            auto v3_rows = [&](auto ci_c, auto q_c) {
-                constexpr int CI = decltype(ci_c)::value, Q = decltype(q_c)::value, CH = CI / 2;
-                float s1[CI], s2[CI];
-#pragma unroll
-                for (int ci = 0; ci < CI; ++ci) s1[ci] = s2[ci] = 0.f;
-                const int npq = (Gt.ph * d.w_in) / Q;
-                for (int gq = tid; gq < npq; gq += 256) {
-                    const int qy = dq(Q * gq, Gt.d_win), px0 = Q * gq - qy * d.w_in;
-                    const int64_t gb_in = ((int64_t)T.b * d.in_ctot + d.in_c0) * HWi + (int64_t)(py0 + qy) * d.w_in + px0;
-                    float pv[CI][Q];
-                    if (gq == tid) {           // (loaded in phase 1)
-#pragma unroll
-                        for (int ci = 0; ci < CI; ++ci)
-#pragma unroll
-                            for (int q = 0; q < Q; ++q) pv[ci][q] = d.gin_accumulate ? pv3[ci][q] : 0.f;
-                    } else {
-#pragma unroll
-                        for (int ci = 0; ci < CI; ++ci) {
-                            const bool ok = ci < d.cin && d.gin_accumulate;
-                            const float* pp = ok ? ws + gin_off + gb_in + (int64_t)ci * HWi : zero;
-#pragma unroll
-                            for (int q = 0; q < Q; ++q) pv[ci][q] = as_gld(pp)[ok ? q : 0];
-                        }
-                    }
-                    f32x2 acc2[CH][Q];
-#pragma unroll
-                    for (int h = 0; h < CH; ++h)
-#pragma unroll
-                        for (int q = 0; q < Q; ++q) acc2[h][q] = f32x2{0.f, 0.f};
-                    for (int co = 0; co < d.cout; ++co) {
-#pragma unroll
-                        for (int ky = 0; ky < K; ++ky) {
-                            const float* grow = gl + co * gplane + (qy + py0 + d.pad - ky - gy0) * Gt.PG + HALO + px0 +
-                                                d.pad - (K - 1);
-                            float gw[K + Q - 1];
-#pragma unroll
-                            for (int t = 0; t < K + Q - 1; ++t) gw[t] = grow[t];
-                            const float* wrow = wD + (co * K + ky) * K * CI;
-#pragma unroll
-                            for (int kx = 0; kx < K; ++kx) {
-                                f32x4 w4[CI / 4];
-#pragma unroll
-                                for (int v = 0; v < CI / 4; ++v) w4[v] = *reinterpret_cast<const f32x4*>(wrow + kx * CI + 4 * v);
-#pragma unroll
-                                for (int q = 0; q < Q; ++q) {
-                                    const float gv = gw[q + K - 1 - kx];
-#pragma unroll
-                                    for (int h = 0; h < CH; ++h) {
-                                        const f32x2 w = f32x2{w4[h >> 1][2 * (h & 1)], w4[h >> 1][2 * (h & 1) + 1]};
-                                        acc2[h][q] = __builtin_elementwise_fma(w, f32x2{gv, gv}, acc2[h][q]);
-                                    }
-                                }
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int ci = 0; ci < CI; ++ci) {
-                        if (ci >= d.cin) break;
-                        const float* ap = alb + (ci * Gt.rh + (py0 - iy0 + qy)) * Gt.P + HALO + px0;
-                        // (the channel's BN constants by uniform LDS reads here, not held across the item)
-                        const float lg = d.in_bn ? i_gam[ci] : 0.f;
-                        const float lb = d.in_bn ? i_sh[ci] + i_mean[ci] * i_sc[ci] : 0.f;
-                        const float lr = d.in_bn ? 1.f / lg : 0.f;
-                        float o[Q];
-#pragma unroll
-                        for (int q = 0; q < Q; ++q) {
-                            const float a = acc2[ci >> 1][q][ci & 1];
-                            if (d.in_bn) {
-                                const float av = ap[q];
-                                const float dbn = av > 0.f ? a : 0.f;
-                                o[q] = pv[ci][q] + lg * dbn;
-                                s1[ci] += dbn;
-                                s2[ci] += dbn * ((av - lb) * lr);
-                            } else {
-                                o[q] = pv[ci][q] + a;
-                            }
-                        }
-                        store_px<Q>(ws + gin_off + gb_in + (int64_t)ci * HWi, o);
-                    }
-                }
-                if (d.in_bn) {
-                    // wave sums (DPP) of the 2 CI channel sums; lane l16 of the kq = 0 lanes takes channel l16's
-                    float v2[2 * CI];
-#pragma unroll
-                    for (int ci = 0; ci < CI; ++ci) {
-                        v2[ci] = s1[ci];
-                        v2[CI + ci] = s2[ci];
-                    }
-                    wave_sums(v2);
-                    float a = 0.f, b = 0.f;
-#pragma unroll
-                    for (int ci = 0; ci < CI; ++ci) {
-                        a = l16 == ci ? v2[ci] : a;
-                        b = l16 == ci ? v2[CI + ci] : b;
-                    }
-                    sd = kq == 0 ? a : 0.f;
-                    sdx = kq == 0 ? b : 0.f;
-                }
-            };
-            const bool q2 = Gt.ph * d.w_in >= 512;
-            if (d.cin <= 4) { if (q2) v3_rows(IntC<4>{}, IntC<2>{}); else v3_rows(IntC<4>{}, IntC<1>{}); }
-            else if (d.cin <= 8) { if (q2) v3_rows(IntC<8>{}, IntC<2>{}); else v3_rows(IntC<8>{}, IntC<1>{}); }
-
-        }
-    }
-#endif
     // ---- phase 4b': input gradient on the VALU (cin <= 4, 5x5, stride 1): Q consecutive pixels of an
     // owned row per thread (4 for cin <= 2, 2 otherwise), all (<= 4) input channels at once.  The
     // weights W[co][ci][ky][kx] are wave-uniform: scalar loads from the parameters (constant address
@@ -2614,16 +2281,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
             lb[ci] = d.in_bn ? i_sh[cc] + i_mean[cc] * i_sc[cc] : 0.f;
             lr[ci] = d.in_bn ? 1.f / lg[ci] : 0.f;
         }
-        // packed over input-channel pairs: WB[((co K + ky) K + kx) CIV + ci]; lane l holds WB[64 j + l] in
-        // wb[j], a tap's channel pair is taken by v_readlane (no LDS traffic for the weights in the loop)
+        // packed over input-channel pairs: WB[((co K + ky) K + kx) CIV + ci], a tap's channel pair by one
+        // broadcast LDS read (as the fused forward's weights)
         auto vdg_rows = [&](auto ci_c) {
             constexpr int CI = decltype(ci_c)::value;     // == CIV
             constexpr int CH = CI / 2;
             constexpr int Q = CI == 2 ? 4 : 2;
-            constexpr int NWB = (2 * KK * CI + 63) / 64;   // cout <= 2 (vop)
-            float wb[NWB];
-    #pragma unroll
-            for (int j = 0; j < NWB; ++j) wb[j] = mid[64 * j + lane];
             const int npq = (Gt.ph * d.w_in) / Q;
             for (int gq = tid; gq < npq; gq += 256) {
                 const int qy = dq(Q * gq, Gt.d_win), px0 = Q * gq - qy * d.w_in;
@@ -2655,14 +2318,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
     #pragma unroll
                             for (int h = 0; h < CH; ++h) {
                                 const int i = ((co * K + ky) * K + kx) * CI + 2 * h;
-                                if (GPI_VDG_WLDS) {
-                                    // the channel pair by one broadcast LDS read (as the fused forward's weights)
-                                    w[h] = *reinterpret_cast<const f32x2*>(mid + i);
-                                } else {
-                                    w[h][0] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wb[i >> 6]), i & 63));
-                                    w[h][1] = __int_as_float(
-                                        __builtin_amdgcn_readlane(__float_as_int(wb[(i + 1) >> 6]), (i + 1) & 63));
-                                }
+                                w[h] = *reinterpret_cast<const f32x2*>(mid + i);
                             }
     #pragma unroll
                             for (int q = 0; q < Q; ++q) {
@@ -2729,13 +2385,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                 }
             }
         } else {
-            // lanes 16 apart share a channel: fold them (v3: wave sums already in the kq = 0 lanes)
-            if (!v3) {
-                sd += __shfl_xor(sd, 16, 64);
-                sdx += __shfl_xor(sdx, 16, 64);
-                sd += __shfl_xor(sd, 32, 64);
-                sdx += __shfl_xor(sdx, 32, 64);
-            }
+            // lanes 16 apart share a channel: fold them
+            sd += __shfl_xor(sd, 16, 64);
+            sdx += __shfl_xor(sdx, 16, 64);
+            sd += __shfl_xor(sd, 32, 64);
+            sdx += __shfl_xor(sdx, 32, 64);
             if (kq == 0) {
                 red[wv * 32 + l16] = sd;
                 red[128 + wv * 32 + l16] = sdx;
@@ -2882,10 +2536,9 @@ constexpr bool no_fold(int i) {
 template <int I>
 conv_kernel_t shape_kernel() {
     constexpr ShapeC s = kShapes[I];
-    // (the fused output conv only with GPI_FUSE_FOLD != 0: see there)
-    if constexpr ((s.fusek != 0 && GPI_FUSE_FOLD == 0) || no_fold(I)) return nullptr;
+    if constexpr (no_fold(I)) return nullptr;
     else if constexpr (s.fwd != 0) return conv_fwd_kernel<s.D_k, s.D_stride, s.D_upsample, s.cp, s.npxk, s.half != 0, I>;
-    else return conv_bwd_kernel<s.D_k, s.D_stride, s.upk, s.fusek != 0, s.half != 0, s.v3 != 0, s.exf != 0, I>;
+    else return conv_bwd_kernel<s.D_k, s.D_stride, s.upk, s.fusek != 0, s.half != 0, s.exf != 0, I>;
 }
 
 // kernel of entry LO + i, entries [LO, LO + n) instantiated here
@@ -2940,10 +2593,6 @@ conv_kernel_t pick(int cp, bool fwd, int npx, bool half, bool ucls = false) {
         // upsampling backward (+1.2-1.6 us per launch)
         if (!fwd && ucls) return half ? conv_bwd_kernel<K, S, 2, false, true> : conv_bwd_kernel<K, S, 2>;
     }
-    if constexpr (K == 3 && S == 1 && UP == 0) {
-        // (the ucls slot carries v3_op for this shape)
-        if (!fwd && ucls) return half ? conv_bwd_kernel<3, 1, 0, false, true, true> : conv_bwd_kernel<3, 1, 0, false, false, true>;
-    }
     if (!fwd) return half ? conv_bwd_kernel<K, S, UP, false, true> : conv_bwd_kernel<K, S, UP>;
     if constexpr (K == 3 && S == 1) {   // the row-pair form (fwd_rows2: 3 to 8 output channels)
         if (npx == NPX_ROWS2) {
@@ -2960,16 +2609,17 @@ conv_kernel_t pick(int cp, bool fwd, int npx, bool half, bool ucls = false) {
     return pick_cp<K, S, UP, 1>(cp, half);
 }
 
-// the backward ops that take the VALU input gradient (GPI_VDG3; the kernel's v3 condition at full tiles)
-bool v3_op(const gpi_conv_desc& d, const ConvGeom& G) {
-    return GPI_VDG3 && d.k == 3 && d.stride == 1 && !d.upsample && d.gin_off >= 0 && d.cin <= 8 && G.ph * d.w_in >= 256;
-}
-
-conv_kernel_t select_kernel(const gpi_conv_desc& d, int cp, bool fwd, int npx, bool half, bool ucls) {
+// fuse: the fused output conv's launch (launch() checks its shape: 5x5 / stride 1), exf its exp-field loss form
+conv_kernel_t select_kernel(const gpi_conv_desc& d, int cp, bool fwd, int npx, bool half, bool ucls, bool fuse,
+                            bool exf) {
+    if (fuse) {
+        if (half) return exf ? conv_bwd_kernel<5, 1, 0, true, true, true> : conv_bwd_kernel<5, 1, 0, true, true>;
+        return exf ? conv_bwd_kernel<5, 1, 0, true, false, true> : conv_bwd_kernel<5, 1, 0, true>;
+    }
     const int key = d.k * 100 + d.stride * 10 + d.upsample;
     switch (key) {
         case 110: return pick<1, 1, 0>(cp, fwd, npx, half);
-        case 310: return pick<3, 1, 0>(cp, fwd, npx, half, ucls);
+        case 310: return pick<3, 1, 0>(cp, fwd, npx, half);
         case 311: return pick<3, 1, 1>(cp, fwd, npx, half, ucls);
         case 320: return pick<3, 2, 0>(cp, fwd, npx, half);
         case 510: return pick<5, 1, 0>(cp, fwd, npx, half);
@@ -3033,10 +2683,8 @@ ShapeC shape_of(const gpi_conv_desc& d, const ConvGeom& G, bool fwd, bool fuse, 
         s.exf = exf;
         s.upk = 0;
     } else if (!fwd) {
-        const bool u = G.ucls != 0 || v3_op(d, G);
         s.half = half;
-        s.upk = (d.upsample && u) ? 2 : d.upsample;
-        s.v3 = d.k == 3 && d.stride == 1 && !d.upsample && u;
+        s.upk = (d.upsample && G.ucls) ? 2 : d.upsample;
     } else {
         // pick(): NPX = 0 (channel groups) only for the stride-1 / stride-2 convs of k <= 3 without upsampling,
         // and its instantiation has no half-tile form
@@ -3105,10 +2753,7 @@ int launch(const gpi_conv_desc& d, const gpi_codec_ctx& c, hipStream_t st, bool 
     if (!fwd && d.gin_off >= 0 && d.stride == 2 && ((d.w_in & 7) || (G.ph & 1))) return GPI_ERR_UNSUPPORTED;
     const int cp = cp_of(d);
     const bool exf = d.epilogue == GPI_EPI_GAUSS_EXP_LOSS;
-    conv_kernel_t k = fuse ? (G.nfull < G.nblocks ? (exf ? conv_bwd_kernel<5, 1, 0, true, true, false, true> : conv_bwd_kernel<5, 1, 0, true, true>)
-                                                  : (exf ? conv_bwd_kernel<5, 1, 0, true, false, false, true> : conv_bwd_kernel<5, 1, 0, true>))
-                           : select_kernel(d, cp, fwd, G.cg > 1 ? 0 : G.npx, G.nfull < G.nblocks,
-                                           G.ucls != 0 || (!fwd && v3_op(d, G)));
+    conv_kernel_t k = select_kernel(d, cp, fwd, G.cg > 1 ? 0 : G.npx, G.nfull < G.nblocks, G.ucls != 0, fuse, exf);
     if (!k) return GPI_ERR_UNSUPPORTED;
     static const float* zero = nullptr;
     if (!zero && !dry) {

@@ -1,8 +1,9 @@
-"""Gaussian helpers (reference bottleneck/utils.py:216-248).
+"""Gaussian helpers and the optimal-effective-property fit (reference bottleneck/utils.py:216-282).
 
 Tensor-level utilities kept with the reference's names and signatures for
 callers outside the fused step (e.g. monitoring); the training step computes
 the same quantities inside the native kernels (head.hip, conv.hip, rom.hip).
+OptimizeEffectiveProperties runs on gpi_rom_fit (gpi/romfit.py).
 """
 import torch
 
@@ -30,3 +31,56 @@ def relative_error(y, y_true):
 
 def relative_error_batched(Y_mean, Y_true):
     return torch.mean(torch.norm(Y_mean - Y_true, dim=1) / torch.norm(Y_true, dim=1)).item()
+
+
+def OptimizeEffectiveProperties(dataset, g, num_iterations=300, lr=1e-2, verbose=True, y_preprocessor=None):
+    """The log effective properties that best reproduce the labels through the ROM g (reference
+    bottleneck/utils.py:250-282): Adam from logX = 0 on MSELoss(g.forward_mean(logX, F_ROM_BC), Y) over
+    every labelled sample.  Returns (logX_effprop, Y_predict, objective, relerr_list): the fitted rows,
+    the prediction of the last iteration (before its update), the objective of every iteration and the
+    batched relative error at iterations 100, 200, ... (of the prediction made one iteration earlier).
+
+    nc = 4 / 8 without a y_preprocessor: one gpi_rom_fit launch (gpi/romfit.py).  Otherwise the same
+    loop through g.forward_mean (gpi_rom) and torch.optim.Adam on the device."""
+    Y = dataset.get('Y')
+    F_ROM_BC = dataset.get('F_ROM_BC')
+    rom = getattr(g, 'rom', None)
+    if y_preprocessor is None and rom is not None and Y.shape[0] > 0:
+        from gpi import romfit
+        if rom.nc in romfit.SUPPORTED_NC:
+            fit = romfit.fit_effective_properties(Y, F_ROM_BC, rom.nc, rom.refine, num_iterations, lr=lr).check()
+            relerr_list = [fit.relerr(n - 1) for n in range(100, num_iterations, 100)]
+            if verbose:
+                for k, e in enumerate(relerr_list):
+                    print("Iteration {} || RelErr : {}".format(100 * (k + 1), e))
+            if num_iterations > 0:
+                Y_predict = g.forward_mean(fit.x_eval, F_ROM_BC).detach()
+            else:
+                Y_predict = None
+            logX_effprop = fit.x.to(Y.dtype).requires_grad_(True)
+            return logX_effprop, Y_predict, fit.objective().tolist(), relerr_list
+
+    if y_preprocessor is not None:
+        Y = y_preprocessor(Y)
+    logX_effprop = torch.zeros(Y.shape[0], g.dim_effective_property, dtype=Y.dtype, device=Y.device,
+                               requires_grad=True)
+    optimizer = torch.optim.Adam([logX_effprop], lr=lr)
+    loss = torch.nn.MSELoss()
+    objective, relerr_list = [], []
+    Y_predict = None
+    for n in range(num_iterations):
+        if n % 100 == 0 and n > 0:
+            with torch.no_grad():
+                myrelerr = relative_error_batched(Y_predict, Y)
+                relerr_list.append(myrelerr)
+            if verbose:
+                print("Iteration {} || RelErr : {}".format(n, myrelerr))
+        Y_predict = g.forward_mean(logX_effprop, F_ROM_BC)
+        if y_preprocessor is not None:
+            Y_predict = y_preprocessor(Y_predict)
+        J = loss(Y_predict, Y)
+        optimizer.zero_grad()
+        J.backward()
+        objective.append(J.item())
+        optimizer.step()
+    return logX_effprop, Y_predict, objective, relerr_list

@@ -112,6 +112,20 @@ __device__ __forceinline__ void bn_mean_invstd(const gpi_stat& st, double n, flo
     invstd = (float)(1.0 / sqrt(var + (double)eps));
 }
 
+// torch.optim.Adam's element update (torch/optim/adam.py single-tensor path, no weight decay /
+// amsgrad / maximize), every rounding spelled out with explicit FMAs so that the separate Adam launch,
+// the fused epilogue + Adam launch (misc.hip) and the ROM fit's resident update (rom.hip) compute
+// bit-identical results:
+//   m.lerp_(g, 1 - beta1);  v.mul_(beta2).addcmul_(g, g, 1 - beta2);
+//   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+__device__ __forceinline__ void adam_element(float g, float& p, float& m, float& v, float beta1, float beta2,
+                                             float eps, float step_size, float bc2_sqrt) {
+    m = fmaf(1.f - beta1, g - m, m);
+    v = fmaf(1.f - beta2, g * g, v * beta2);
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = fmaf(-step_size, m / denom, p);
+}
+
 // ---------------------------------------------------------------- Philox4x32-10
 struct uint4_ { uint32_t x, y, z, w; };
 

@@ -43,19 +43,6 @@ __global__ __launch_bounds__(256) void step_epilogue_kernel(gpi_step_epilogue_de
     }
 }
 
-// torch.optim.Adam's element update (torch/optim/adam.py single-tensor path, no weight decay /
-// amsgrad / maximize), every rounding spelled out with explicit FMAs so that the separate Adam launch
-// and the fused epilogue + Adam launch compute bit-identical results:
-//   m.lerp_(g, 1 - beta1);  v.mul_(beta2).addcmul_(g, g, 1 - beta2);
-//   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
-__device__ __forceinline__ void adam_element(float g, float& p, float& m, float& v, float beta1, float beta2,
-                                             float eps, float step_size, float bc2_sqrt) {
-    m = fmaf(1.f - beta1, g - m, m);
-    v = fmaf(1.f - beta2, g * g, v * beta2);
-    const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = fmaf(-step_size, m / denom, p);
-}
-
 // The step epilogue with Adam fused in (single-process steps: no all-reduce between the gradient
 // delivery and the update): element i's fp64 gradient -> grad[i] -> Adam on p[i], m[i], v[i], plus the
 // epilogue's scratch / subset / dropout duties.  The step counter and the RNG offset are read by every
@@ -536,7 +523,7 @@ extern "C" int gpi_struct_sizes(int64_t* out, int n) {
                          (int64_t)sizeof(gpi_fom_desc), (int64_t)sizeof(gpi_random_field_desc),
                          (int64_t)sizeof(gpi_vo_sparse), (int64_t)sizeof(gpi_draw_item),
                          (int64_t)sizeof(gpi_bn_exchange_desc), (int64_t)sizeof(gpi_bn_eval_item),
-                         (int64_t)sizeof(gpi_vo_energy_desc)};
+                         (int64_t)sizeof(gpi_vo_energy_desc), (int64_t)sizeof(gpi_rom_fit_desc)};
     const int k = (int)(sizeof(s) / sizeof(s[0]));
     if (!out || n < k) return GPI_ERR_ARG;
     for (int i = 0; i < k; ++i) out[i] = s[i];

@@ -14,7 +14,8 @@
 //   * LOGLIK mode fuses DiagonalGaussianLogLikelihood(Y, mu_y, 2 logsigma_y)
 //     and its adjoint: lambda = K_II^{-1} W^T dmu,
 //     dJ/dc_pq = -(lambda_p - lambda_q)(u_p - u_q), dJ/dkappa_t = 1/2 sum over
-//     its two legs, dJ/dx = dJ/dkappa * exp(x).
+//     its two legs, dJ/dx = dJ/dkappa * exp(x);
+//   * gpi_rom_fit (rom_fit_kernel, below): OptimizeEffectiveProperties' whole Adam loop over x in one launch.
 #include "common.h"
 #include <stdlib.h>
 
@@ -893,6 +894,247 @@ __global__ __launch_bounds__(64) void rom_lane_kernel(gpi_rom_desc d) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// rom_fit_kernel<NC> (gpi_rom_fit; nc = 4 / 8): ONE WAVE64 PER SAMPLE runs every Adam iteration of
+// OptimizeEffectiveProperties (bottleneck/utils.py:250-282) in one launch.  Row n of the gradient
+// depends on row n alone (the MSE mean's 1 / (n_total d_y) is a constant), so the workgroups never talk.
+//   setup      one pass over Y_n: lane q owns coarse square q (interp()'s partition of the fine free
+//              nodes) and sums, in fp64 and in a fixed order, its nodes' shares of b_n = W^T Y_n,
+//              c_n = |Y_n|^2 and G = W^T W (per square: 4 diagonal and 5 edge entries -- the "/"
+//              triangles never couple a square's +x and +y corners, hence <= 7 non-zeros per row);
+//              the squares' shares meet per coarse node in LDS (gather, fixed order: no atomics).
+//   iteration  kappa = exp(x) + 1e-8 -> band rows -> chol_inv_wave (Z = L^{-1}) -> u = Z^T (Z rhs) ->
+//              fp64: G u, ss = u^T (G u - 2 b) + c, g_u = gscale (G u - b) -> lambda = Z^T (Z g_u) ->
+//              dJ/dx by the edge formula of rom_kernel -> adam_element on the lane's x, m, v.
+// x, m, v live in registers (triangle t = lane + 64 k); an iteration touches coarse quantities only, its
+// cost does not depend on the refinement.  No cross-workgroup traffic, no waits.
+
+// out = Z^T (Z v) = K^{-1} v for one wave (kinv_apply's two triangular mat-vecs without the split over
+// waves): lane i owns row i; v (in / out) and w are 64-float LDS vectors.  Four partial sums in a fixed
+// order.  Ends with a barrier.
+template <int NC>
+__device__ __forceinline__ void kinv_apply_wave(const float* __restrict__ z, float* v, float* w) {
+    constexpr int NI = (NC - 1) * (NC + 1);
+    const int i = threadIdx.x, ic = i < NI ? i : NI - 1;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < NI; ++k)              // (Z v)_i = sum_{k <= i} Z[i][k] v_k
+        a[k & 3] = fmaf(k <= i ? z[ic * KINV_P + k] : 0.f, v[k], a[k & 3]);
+    w[i] = i < NI ? (a[0] + a[1]) + (a[2] + a[3]) : 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[c] = 0.f;
+#pragma unroll
+    for (int k = 0; k < NI; ++k)              // (Z^T w)_i = sum_{k >= i} Z[k][i] w_k
+        a[k & 3] = fmaf(k >= i ? z[k * KINV_P + i] : 0.f, w[k], a[k & 3]);
+    if (i < NI) v[i] = (a[0] + a[1]) + (a[2] + a[3]);
+    __syncthreads();
+}
+
+template <int NC>
+struct RomFitLds {   // float offsets after the fp64 block (every block a multiple of 4 floats)
+    static constexpr int NI = (NC - 1) * (NC + 1), NN = (NC + 1) * (NC + 1), NT2 = 2 * NC * NC;
+    static constexpr int NNP = (NN + 3) & ~3;
+    static constexpr int ND = 5 * NN + (NN & 1);                 // doubles: G [4][NN], b [NN]
+    static constexpr int KP = 0, L = KP + NT2, U = L + ((NI * NC + 3) & ~3), LAM = U + NNP, FS = LAM + NNP,
+                         BV = FS + NNP, WV = BV + 64, Z = WV + 64, END = Z + ((NI * KINV_P + 3) & ~3);
+    static constexpr size_t bytes = sizeof(double) * ND + sizeof(float) * END;
+    static_assert(sizeof(double) * 13 * NC * NC <= sizeof(float) * NI * KINV_P, "setup partials fit in Z");
+};
+
+template <int NC>
+__global__ __launch_bounds__(64) void rom_fit_kernel(gpi_rom_fit_desc d, double gscale) {
+    using S = RomFitLds<NC>;
+    constexpr int W = NC, BW = NC - 1, NI = S::NI, NN = S::NN, NT2 = S::NT2, NQ = NC * NC;
+    constexpr int KX = (NT2 + 63) / 64;                          // triangles per lane
+    extern __shared__ __attribute__((aligned(16))) double smd[];
+    double* G = smd;                   // [4][NN]: (p,p), (p,p+1), (p,p+nc+1), (p,p+nc+2)
+    double* bn = G + 4 * NN;           // [NN] W^T Y
+    float* sm = (float*)(smd + S::ND);
+    float* kp = sm + S::KP;            // [NT2] kappa
+    float* L = sm + S::L;              // [NI * W] band rows
+    float* u = sm + S::U;              // [NN] coarse solution
+    float* lam = sm + S::LAM;          // [NN] adjoint (0 on the Dirichlet nodes)
+    float* Fs = sm + S::FS;            // [NN] F_ROM_BC
+    float* bv = sm + S::BV;            // [64] right-hand side / solution of the interior system
+    float* wv = sm + S::WV;            // [64] kinv_apply_wave scratch
+    float* z = sm + S::Z;              // [NI][KINV_P] Z = L^{-1}; the setup's per-square sums before
+    const int lane = threadIdx.x;
+    const int64_t s = blockIdx.x;
+    const int r = d.refine, nf = NC * r;
+    const int64_t dy = (int64_t)(nf + 1) * (nf - 1);
+
+    // ---- setup: b = W^T Y, c = |Y|^2, G = W^T W (fp64, fixed order)
+    for (int e = lane; e < NN; e += 64) Fs[e] = d.F[s * NN + e];
+    double cc = 0.0;
+    {
+        double pb[4] = {0.0, 0.0, 0.0, 0.0};
+        double pg[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // 00 11 22 33 01 02 03 13 23
+        if (lane < NQ) {
+            const int I = lane % NC, J = lane / NC;
+            const int i0 = I == 0 ? 1 : I * r, i1 = (I + 1) * r - 1;     // free columns (inclusive)
+            const int rows = J == NC - 1 ? r + 1 : r;
+            const double rinv = 1.0 / (double)r;
+            for (int jj = 0; jj < rows; ++jj) {
+                const float* yrow = d.Y + s * dy + (int64_t)(J * r + jj) * (nf - 1) - 1;
+                const double eta = (double)jj * rinv;
+                for (int i = i0; i <= i1; ++i) {
+                    const double y = (double)yrow[i];
+                    const double xi = (double)(i - I * r) * rinv;
+                    double w0, w1, w2, w3;                               // corners v0, +x, +y, +x+y
+                    if (xi >= eta) { w0 = 1.0 - xi; w1 = xi - eta; w2 = 0.0; w3 = eta; }
+                    else { w0 = 1.0 - eta; w1 = 0.0; w2 = eta - xi; w3 = xi; }
+                    cc = fma(y, y, cc);
+                    pb[0] = fma(w0, y, pb[0]); pb[1] = fma(w1, y, pb[1]);
+                    pb[2] = fma(w2, y, pb[2]); pb[3] = fma(w3, y, pb[3]);
+                    pg[0] = fma(w0, w0, pg[0]); pg[1] = fma(w1, w1, pg[1]);
+                    pg[2] = fma(w2, w2, pg[2]); pg[3] = fma(w3, w3, pg[3]);
+                    pg[4] = fma(w0, w1, pg[4]); pg[5] = fma(w0, w2, pg[5]); pg[6] = fma(w0, w3, pg[6]);
+                    pg[7] = fma(w1, w3, pg[7]); pg[8] = fma(w2, w3, pg[8]);
+                }
+            }
+        }
+        double* sq = (double*)z;       // [NQ][13]
+        if (lane < NQ) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) sq[lane * 13 + c] = pb[c];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) sq[lane * 13 + 4 + c] = pg[c];
+        }
+        cc = wave_sum_d(cc);
+        __syncthreads();
+        for (int e = lane; e < NN; e += 64) {
+            const int I = e % (NC + 1), J = e / (NC + 1);
+            // the squares that hold node e, as their corner 3, 2, 1, 0
+            const int q3 = (I - 1) + NC * (J - 1), q2 = I + NC * (J - 1), q1 = (I - 1) + NC * J, q0 = I + NC * J;
+            const bool h3 = I > 0 && J > 0, h2 = I < NC && J > 0, h1 = I > 0 && J < NC, h0 = I < NC && J < NC;
+            double b = 0.0, gd = 0.0, gx = 0.0, gy = 0.0, gxy = 0.0;
+            if (h3) { b += sq[q3 * 13 + 3]; gd += sq[q3 * 13 + 4 + 3]; }
+            if (h2) { b += sq[q2 * 13 + 2]; gd += sq[q2 * 13 + 4 + 2]; gx += sq[q2 * 13 + 4 + 8]; }
+            if (h1) { b += sq[q1 * 13 + 1]; gd += sq[q1 * 13 + 4 + 1]; gy += sq[q1 * 13 + 4 + 7]; }
+            if (h0) {
+                b += sq[q0 * 13 + 0]; gd += sq[q0 * 13 + 4 + 0]; gx += sq[q0 * 13 + 4 + 4];
+                gy += sq[q0 * 13 + 4 + 5]; gxy = sq[q0 * 13 + 4 + 6];
+            }
+            bn[e] = b;
+            G[e] = gd; G[NN + e] = gx; G[2 * NN + e] = gy; G[3 * NN + e] = gxy;
+        }
+        __syncthreads();               // z is free from here on
+    }
+    if (lane == 0 && d.ynorm2) d.ynorm2[s] = cc;
+    if (d.iters <= 0) return;
+
+    float xr[KX], mr[KX], vr[KX];
+#pragma unroll
+    for (int k = 0; k < KX; ++k) {
+        const int t = lane + 64 * k;
+        const bool ok = t < NT2;
+        xr[k] = ok ? d.x[s * d.x_stride + t] : 0.f;
+        mr[k] = ok && d.m ? d.m[s * NT2 + t] : 0.f;
+        vr[k] = ok && d.v ? d.v[s * NT2 + t] : 0.f;
+    }
+    bool bad = false;
+    for (int it = 0; it < d.iters; ++it) {
+        const bool last = it == d.iters - 1;
+#pragma unroll
+        for (int k = 0; k < KX; ++k) {
+            const int t = lane + 64 * k;
+            if (t < NT2) {
+                const float kv = expf(xr[k]) + 1e-8f;
+                bad |= !(kv > 1e-12f);
+                kp[t] = kv;
+                if (last && d.x_eval) d.x_eval[s * NT2 + t] = xr[k];
+            }
+        }
+        __syncthreads();
+        // ---- the interior system (banded lower) + rhs, as rom_kernel_fast
+        if (lane < NI) {
+            const int ii = lane;
+            const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
+            const int p = I + (NC + 1) * J;
+            const float chl = c_h(kp, NC, I - 1, J), chr = c_h(kp, NC, I, J);
+            const float cvd = J > 0 ? c_v(kp, NC, I, J - 1) : 0.f;
+            const float cvu = J < NC ? c_v(kp, NC, I, J) : 0.f;
+            float* row = L + ii * W;
+#pragma unroll
+            for (int t = 0; t < W; ++t) row[t] = 0.f;
+            row[0] = chl + chr + cvd + cvu;
+            if (I - 1 >= 1) row[1] += -chl;
+            if (J >= 1) row[BW] += -cvd;
+            float rhs = Fs[p];
+            if (I - 1 == 0) rhs += chl * Fs[p - 1];
+            if (I + 1 == NC) rhs += chr * Fs[p + 1];
+            bv[ii] = rhs;
+        }
+        __syncthreads();
+        chol_inv_wave<NC>(L, z);
+        __syncthreads();
+        kinv_apply_wave<NC>(z, bv, wv);
+        for (int e = lane; e < NN; e += 64) {
+            const int I = e % (NC + 1), J = e / (NC + 1);
+            const float ue = (I == 0 || I == NC) ? Fs[e] : bv[J * (NC - 1) + (I - 1)];
+            u[e] = ue;
+            if (last && d.uc) d.uc[s * NN + e] = ue;
+        }
+        __syncthreads();
+        // ---- fp64: G u, the squared residual and its gradient
+        double ssp = 0.0;
+        for (int e = lane; e < NN; e += 64) {
+            const int I = e % (NC + 1), J = e / (NC + 1);
+            double gu = G[e] * (double)u[e];
+            if (I > 0) gu = fma(G[NN + e - 1], (double)u[e - 1], gu);
+            if (I < NC) gu = fma(G[NN + e], (double)u[e + 1], gu);
+            if (J > 0) gu = fma(G[2 * NN + e - (NC + 1)], (double)u[e - (NC + 1)], gu);
+            if (J < NC) gu = fma(G[2 * NN + e], (double)u[e + (NC + 1)], gu);
+            if (I > 0 && J > 0) gu = fma(G[3 * NN + e - (NC + 2)], (double)u[e - (NC + 2)], gu);
+            if (I < NC && J < NC) gu = fma(G[3 * NN + e], (double)u[e + (NC + 2)], gu);
+            ssp = fma((double)u[e], gu - 2.0 * bn[e], ssp);
+            if (I > 0 && I < NC) bv[J * (NC - 1) + (I - 1)] = (float)(gscale * (gu - bn[e]));
+        }
+        const double ss = wave_sum_d(ssp) + cc;
+        bad |= !(fabs(ss) <= 1.7976931348623157e308);
+        if (lane == 0 && d.sumsq) d.sumsq[(int64_t)it * d.n + s] = ss;
+        __syncthreads();
+        // ---- adjoint lambda = K^{-1} g_u (interior), dJ/dx per coarse triangle, Adam
+        kinv_apply_wave<NC>(z, bv, wv);
+        for (int e = lane; e < NN; e += 64) {
+            const int I = e % (NC + 1), J = e / (NC + 1);
+            lam[e] = (I == 0 || I == NC) ? 0.f : bv[J * (NC - 1) + (I - 1)];
+        }
+        __syncthreads();
+        const int64_t step = d.step0 + it + 1;
+        const double bc1 = 1.0 - pow((double)d.beta1, (double)step);
+        const double bc2 = 1.0 - pow((double)d.beta2, (double)step);
+        const float step_size = (float)((double)d.lr / bc1);
+        const float bc2_sqrt = (float)sqrt(bc2);
+#pragma unroll
+        for (int k = 0; k < KX; ++k) {
+            const int t = lane + 64 * k;
+            if (t < NT2) {
+                const int q = t >> 1, ul = t & 1;
+                const int I = q % NC, J = q / NC;
+                const int v0 = I + (NC + 1) * J, v1 = v0 + 1, v2 = v0 + (NC + 1), v3 = v2 + 1;
+                float dk;
+                if (!ul) dk = -(lam[v0] - lam[v1]) * (u[v0] - u[v1]) - (lam[v1] - lam[v3]) * (u[v1] - u[v3]);
+                else dk = -(lam[v2] - lam[v3]) * (u[v2] - u[v3]) - (lam[v0] - lam[v2]) * (u[v0] - u[v2]);
+                const float g = 0.5f * dk * (kp[t] - 1e-8f);
+                adam_element(g, xr[k], mr[k], vr[k], d.beta1, d.beta2, d.eps, step_size, bc2_sqrt);
+            }
+        }
+        __syncthreads();               // kp, u, lam, bv are rewritten by the next iteration
+    }
+#pragma unroll
+    for (int k = 0; k < KX; ++k) {
+        const int t = lane + 64 * k;
+        if (t < NT2) {
+            d.x[s * d.x_stride + t] = xr[k];
+            if (d.m) d.m[s * NT2 + t] = mr[k];
+            if (d.v) d.v[s * NT2 + t] = vr[k];
+        }
+    }
+    if (bad && d.flag) atomicOr(d.flag, 1);
+}
+
 }  // namespace
 
 #ifdef GPI_PHASE_TIMING
@@ -904,6 +1146,22 @@ extern "C" int gpi_debug_rom_stamps(unsigned long long* out) {
     return GPI_OK;
 }
 #endif
+
+extern "C" int gpi_rom_fit(const gpi_rom_fit_desc* d, void* stream) {
+    if (!d || d->nc < 2 || d->refine < 1 || d->n < 0 || d->iters < 0 || d->n_total < 0 || d->step0 < 0) return GPI_ERR_ARG;
+    if ((d->nc != 4 && d->nc != 8) || (int64_t)d->nc * d->refine > 4096) return GPI_ERR_UNSUPPORTED;
+    if (d->n == 0) return GPI_OK;
+    if (!d->Y || !d->F || !d->x || d->x_stride < 2 * d->nc * d->nc || !d->m != !d->v) return GPI_ERR_ARG;
+    const int64_t nf = (int64_t)d->nc * d->refine, dy = (nf + 1) * (nf - 1);
+    // d/du of the MSE mean: 2 / (n_total d_y) (G u - b)
+    const double gscale = 2.0 / ((double)(d->n_total ? d->n_total : d->n) * (double)dy);
+    if (d->nc == 8)
+        hipLaunchKernelGGL(rom_fit_kernel<8>, dim3(d->n), dim3(64), RomFitLds<8>::bytes, (hipStream_t)stream, *d, gscale);
+    else
+        hipLaunchKernelGGL(rom_fit_kernel<4>, dim3(d->n), dim3(64), RomFitLds<4>::bytes, (hipStream_t)stream, *d, gscale);
+    GPI_CHECK_LAUNCH();
+    return GPI_OK;
+}
 
 extern "C" int gpi_rom(const gpi_rom_desc* d, void* stream) {
     if (!d || !d->x || !d->F || d->nc < 2 || d->nc > 12 || d->refine < 1 || d->n < 0) return GPI_ERR_ARG;

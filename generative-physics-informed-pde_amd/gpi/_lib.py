@@ -111,6 +111,13 @@ class RomDesc(C.Structure):
                 ('x_mu', vp), ('x_ls', vp), ('x_eps', vp)]
 
 
+class RomFitDesc(C.Structure):
+    _fields_ = [('nc', i32), ('refine', i32), ('n', i32), ('iters', i32), ('n_total', i64),
+                ('Y', vp), ('F', vp), ('x', vp), ('x_stride', i64), ('m', vp), ('v', vp), ('step0', i64),
+                ('lr', f32), ('beta1', f32), ('beta2', f32), ('eps', f32),
+                ('sumsq', vp), ('ynorm2', vp), ('x_eval', vp), ('uc', vp), ('flag', vp)]
+
+
 CGR_AUTO, CGR_BAND, CGR_STREAM, CGR_GENERAL = 0, 1, 2, 3
 
 
@@ -224,7 +231,7 @@ class BnExchangeDesc(C.Structure):
 STRUCTS = [Stat, Groups, ConvDesc, CodecCtx, ReduceItem, HeadDesc, GemmItem, RomDesc, ResidualDesc, AdamDesc,
            VoQueryDesc, VoMomentsDesc, VoConditionDesc, VoPrecisionDesc, GpSampleDesc,
            VoGalerkinDesc, StepEpilogueDesc, FomDesc, RandomFieldDesc, VoSparse, DrawItem, BnExchangeDesc,
-           BnEvalItem, VoEnergyDesc]
+           BnEvalItem, VoEnergyDesc, RomFitDesc]
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -255,6 +262,7 @@ SIGNATURES = {
     'gpi_head_backward': (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp, vp]),
     'gpi_outer_gemm': (C.c_int, [C.POINTER(GemmItem), C.c_int, vp, vp, vp]),
     'gpi_rom': (C.c_int, [C.POINTER(RomDesc), vp]),
+    'gpi_rom_fit': (C.c_int, [C.POINTER(RomFitDesc), vp]),
     'gpi_cgr_residual': (C.c_int, [C.POINTER(ResidualDesc), vp]),
     'gpi_grad_finalize': (C.c_int, [vp, vp, i64, C.c_int, vp, vp]),
     'gpi_adam': (C.c_int, [C.POINTER(AdamDesc), vp]),

@@ -241,6 +241,38 @@ typedef struct gpi_rom_desc {
     const float* x_eps;
 } gpi_rom_desc;
 
+/* Optimal effective properties (OptimizeEffectiveProperties, bottleneck/utils.py:250-282): per sample n,
+ * `iters` Adam steps on x_n of  J = 1 / (n_total d_y) sum_n |W u(x_n) - Y_n|^2  (MSELoss of
+ * forward_mean against the labels), all iterations of all samples in ONE launch.  The samples only
+ * couple through the constant 1 / (n_total d_y), so one wave64 per sample runs the whole loop with
+ * x and the Adam moments in registers.  The fine grid is read once: with G = W^T W (<= 7 non-zeros
+ * per row), b_n = W^T Y_n and c_n = |Y_n|^2 (all fp64),
+ *   |W u - Y_n|^2 = u^T G u - 2 b_n^T u + c_n,   d/du = 2 (G u - b_n),
+ * and an iteration is  kappa = exp(x) + 1e-8 -> K(kappa) -> banded Cholesky -> u -> the fp64 residual
+ * -> adjoint solve with the same factor -> dJ/dx by gpi_rom's edge formula -> torch's Adam update
+ * (adam_element, bias corrections of step step0 + i + 1).  Results depend on nothing but the sample's
+ * own rows and the scalars: any split of the batch (with n_total fixed) or of the iterations (with
+ * m, v, step0 carried over) gives the same bits.  nc = 4 and 8 (GPI_ERR_UNSUPPORTED otherwise), any
+ * refine >= 1 with nc refine <= 4096.  n = 0 launches nothing. */
+typedef struct gpi_rom_fit_desc {
+    int32_t nc, refine, n, iters;
+    int64_t n_total;           /* the N of the MSE mean; 0: n */
+    const float* Y;            /* [n, d_y] labels */
+    const float* F;            /* [n, (nc+1)^2] F_ROM_BC */
+    float* x;                  /* [n, 2 nc^2] log effective properties, rows at x_stride; in / out */
+    int64_t x_stride;
+    float* m;                  /* optional Adam moments [n, 2 nc^2] (dense), in / out; both or neither. */
+    float* v;                  /*   NULL: the fit starts from zero moments and does not return them */
+    int64_t step0;             /* Adam steps already taken on these rows (0 for a fresh fit) */
+    float lr, beta1, beta2, eps;
+    double* sumsq;             /* optional [iters, n]: |W u(x) - Y_n|^2 at every evaluation */
+    double* ynorm2;            /* optional [n]: |Y_n|^2 */
+    float* x_eval;             /* optional [n, 2 nc^2]: the x the last iteration evaluated (before its update) */
+    float* uc;                 /* optional [n, (nc+1)^2]: the coarse solution of that evaluation */
+    int32_t* flag;             /* optional: set to 1 when a sample meets kappa <= 1e-12 or a non-finite residual;
+                                  the other samples are unaffected */
+} gpi_rom_fit_desc;
+
 /* Coarse-grained residual on the fine grid (VirtualObservables CGR query,
  * VirtualObservables.py:57-69,297-321 + physics/LinearElliptic.py:137-159):
  *   r = W^T [K_f(kappa) yhat]_free  (= Gamma y - alpha),
@@ -639,6 +671,7 @@ int gpi_head_backward(const gpi_head_desc* d, const float* params, float* ws, do
 int gpi_outer_gemm(const gpi_gemm_item* items, int n_items, const float* ws, double* gacc, void* stream);
 
 int gpi_rom(const gpi_rom_desc* d, void* stream);
+int gpi_rom_fit(const gpi_rom_fit_desc* d, void* stream);
 int gpi_cgr_residual(const gpi_residual_desc* d, void* stream);
 
 /* Virtual observables: rows per VO sample for a flag set (or a negative error). */

@@ -26,8 +26,10 @@ class ROM(object):
 
     @classmethod
     def FromPhysics(cls, physics, dtype=torch.float32, device=None):
-        """physics: the 'rom' LinearEllipticPhysics (ROM.py:37-57); cap of 290 cells kept (ROM.py:43-44)."""
-        if physics.grid.num_cells > 290:
+        """physics: the 'rom' LinearEllipticPhysics (ROM.py:37-57).  The reference caps the mesh at 290 cells
+        (ROM.py:43-44: its dense tensor M grows with n_c^2 n_T); nothing dense is built here, so the cap is the
+        native solve's, 16 x 16 squares = 512 cells (gpi_rom: nc <= 16)."""
+        if physics.grid.num_cells > 512:
             raise Exception('ROM exceeds intended maximum size')
         return cls(physics.grid, physics.refine_to_fom, dtype=dtype, device=device)
 

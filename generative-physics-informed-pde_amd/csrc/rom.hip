@@ -15,6 +15,9 @@
 //     and its adjoint: lambda = K_II^{-1} W^T dmu,
 //     dJ/dc_pq = -(lambda_p - lambda_q)(u_p - u_q), dJ/dkappa_t = 1/2 sum over
 //     its two legs, dJ/dx = dJ/dkappa * exp(x);
+//   * nc = 4 / 8: rom_kernel_fast (Z = L^{-1} by one wave) and rom_lane_kernel; nc = 16: rom_kernel_fast<16> with
+//     the factorisation and the band sweeps by one wave whose lanes share the window (chol16_wave, band_sweep16)
+//     and rom16_coarse_kernel; any other nc <= 16, and GPI_ROM_SLOW=1: the barrier-per-step rom_kernel;
 //   * gpi_rom_fit (rom_fit_kernel, below): OptimizeEffectiveProperties' whole Adam loop over x in one launch.
 #include "common.h"
 #include <stdlib.h>
@@ -531,9 +534,157 @@ __device__ __forceinline__ void kinv_apply(const float* __restrict__ z, const fl
     __syncthreads();
 }
 
+// ---------------------------------------------------------------------------------------------
+// nc = 16 (NI = 255 unknowns, bandwidth 15): the factorisation and the band sweeps by ONE WAVE, the
+// window of the right-looking band Cholesky distributed over its lanes.
+//   * chol16_wave: the 16 x 16 window of the trailing matrix lives in circular slots (row i mod 16,
+//     column j mod 16), four column slots per lane: lane = 4 (i mod 16) + q holds columns 4 q .. 4 q + 3
+//     of row i.  Step k (slot c = k mod 16, static: the steps are 16 template instances): the pivot by
+//     v_readlane + v_rsq, column k scaled in place (every lane gets its row's entry by a quad broadcast
+//     DPP), the column entries of the lane's four column slots by ds_bpermute, four FMAs, and row
+//     k + 16 enters the slots row k leaves.  No LDS round trip and no barrier on the chain.  Column k
+//     goes to LDS in both orientations (Lc[k][t] = L(k + t, k), Lr[i][t] = L(i, i - t), slot 0 of
+//     either = 1 / L(k,k)) for the sweeps, and step k of the forward substitution of the right-hand
+//     side rides along (column k is final).
+//   * band_sweep16: forward (L y = b, axpy form over Lc) or backward (L^T x = y, axpy form over Lr)
+//     substitution; lane (i mod 16) owns element i of the moving 16-window, so a step is
+//     v_readlane, a multiply and one FMA, the band column prefetched from LDS off the chain.
+constexpr int R16_NI = 255;
+constexpr int R16_LR = (R16_NI + 16) * 16;   // Lr rows k + t of the last steps run past NI (never read)
+constexpr int R16_LC = R16_NI * 16;
+
+// LDS written by some lanes of this wave is read by others: order it for the compiler and the hardware
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ float readlane_f(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+struct Chol16 {
+    float s[4];   // slots (ri, 4 q + m)
+    float bw;     // right-hand side entry of row slot ri (the same in the quad's four lanes)
+    int bp[4];    // ds_bpermute byte address of a lane of row slot 4 q + m
+    int lane, ri, q;
+};
+
+// the system's rows: diagonal, first sub-diagonal, 15th sub-diagonal at dg[i * as], o1[i * as], o15[i * as]
+struct Band16 {
+    const float *dg, *o1, *o15;
+    int as;
+};
+
+template <int C>
+__device__ __forceinline__ void chol16_step(Chol16& w, int k, const Band16& A, float* __restrict__ Lr,
+                                            float* __restrict__ Lc, float* b) {
+    if (k >= R16_NI) return;
+    // row k + 16 (identity past the end), read ahead of the chain
+    const bool has = k + 16 < R16_NI;
+    const int kn = has ? k + 16 : k;
+    float dg = A.dg[kn * A.as], o1 = A.o1[kn * A.as], o15 = A.o15[kn * A.as], bn = b[kn];
+    dg = has ? dg : 1.f;
+    o1 = has ? o1 : 0.f;
+    o15 = has ? o15 : 0.f;
+    bn = has ? bn : 0.f;
+    const float piv = readlane_f(w.s[C & 3], 4 * C + (C >> 2));
+    const float inv = __builtin_amdgcn_rsqf(piv);
+    // this lane's row entry of column k: slot (ri, C) is register C & 3 of the quad's lane C >> 2
+    const float xc = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(w.s[C & 3]), (C >> 2) * 0x55, 0xf, 0xf, false));
+    const float li = xc * inv;                      // L(i, k) of this lane's row (row k itself: L(k,k))
+    float l[4];                                     // L(j, k) of this lane's four column slots
+#pragma unroll
+    for (int m = 0; m < 4; ++m) l[m] = __int_as_float(__builtin_amdgcn_ds_bpermute(w.bp[m], __float_as_int(li)));
+    const float yk = readlane_f(w.bw, 4 * C) * inv; // forward substitution step k
+    w.bw = fmaf(-li, yk, w.bw);
+    const int t = (w.ri - C) & 15;                  // this lane's row is k + t
+    const float val = t == 0 ? inv : li;
+    if (w.q == 0) {
+        Lr[(k + t) * 16 + t] = val;
+        if (Lc) Lc[k * 16 + t] = val;
+    }
+    if (w.lane == 0) b[k] = yk;
+    const bool inq = w.ri == C;                     // row k leaves, row k + 16 enters its slots
+#pragma unroll
+    for (int m = 0; m < 4; ++m) w.s[m] = inq ? 0.f : fmaf(-li, l[m], w.s[m]);
+    constexpr int C1 = (C + 15) & 15, C15 = (C + 1) & 15;   // column slots of k + 15 and k + 1
+    if (w.lane == 4 * C + (C >> 2)) w.s[C & 3] = dg;
+    if (w.lane == 4 * C + (C1 >> 2)) w.s[C1 & 3] = o1;
+    if (w.lane == 4 * C + (C15 >> 2)) w.s[C15 & 3] = o15;
+    w.bw = inq ? bn : w.bw;
+}
+
+// K = L L^T of the 255 x 255 band system A and y = L^{-1} b (in place of b), by the calling wave.
+// Lc may be null (no forward sweep will follow).
+__device__ __forceinline__ void chol16_wave(const Band16& A, float* __restrict__ Lr, float* __restrict__ Lc, float* b) {
+    Chol16 w;
+    w.lane = threadIdx.x & 63;
+    w.ri = w.lane >> 2;
+    w.q = w.lane & 3;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int j = 4 * w.q + m, t = w.ri - j;
+        w.bp[m] = 4 * (4 * j);
+        float v = 0.f;
+        if (t == 0) v = A.dg[w.ri * A.as];
+        if (t == 1) v = A.o1[w.ri * A.as];
+        if (t == 15) v = A.o15[w.ri * A.as];
+        w.s[m] = v;
+    }
+    w.bw = b[w.ri];
+    for (int k0 = 0; k0 < R16_NI; k0 += 16) {
+        chol16_step<0>(w, k0 + 0, A, Lr, Lc, b);
+        chol16_step<1>(w, k0 + 1, A, Lr, Lc, b);
+        chol16_step<2>(w, k0 + 2, A, Lr, Lc, b);
+        chol16_step<3>(w, k0 + 3, A, Lr, Lc, b);
+        chol16_step<4>(w, k0 + 4, A, Lr, Lc, b);
+        chol16_step<5>(w, k0 + 5, A, Lr, Lc, b);
+        chol16_step<6>(w, k0 + 6, A, Lr, Lc, b);
+        chol16_step<7>(w, k0 + 7, A, Lr, Lc, b);
+        chol16_step<8>(w, k0 + 8, A, Lr, Lc, b);
+        chol16_step<9>(w, k0 + 9, A, Lr, Lc, b);
+        chol16_step<10>(w, k0 + 10, A, Lr, Lc, b);
+        chol16_step<11>(w, k0 + 11, A, Lr, Lc, b);
+        chol16_step<12>(w, k0 + 12, A, Lr, Lc, b);
+        chol16_step<13>(w, k0 + 13, A, Lr, Lc, b);
+        chol16_step<14>(w, k0 + 14, A, Lr, Lc, b);
+        chol16_step<15>(w, k0 + 15, A, Lr, Lc, b);
+    }
+    wave_sync();
+}
+
+// FWD: b <- L^{-1} b over Lc; else b <- L^{-T} b over Lr.  By the calling wave (its four rows of 16
+// lanes run the same sweep; lane k mod 16 of row 0 stores).
+template <bool FWD>
+__device__ __forceinline__ void band_sweep16(const float* __restrict__ Lb, float* b) {
+    const int lane = threadIdx.x & 63, l16 = lane & 15;
+    float w = b[FWD ? l16 : (R16_NI - 1) - ((R16_NI - 1 - l16) & 15)];
+#pragma unroll 4
+    for (int n = 0; n < R16_NI; ++n) {
+        const int k = FWD ? n : R16_NI - 1 - n;
+        const int t = (FWD ? l16 - k : k - l16) & 15;       // this lane's element is k + t (FWD) / k - t
+        const float lv = Lb[k * 16 + t], inv = Lb[k * 16];
+        const int kn = FWD ? k + 16 : k - 16;
+        const bool has = FWD ? kn < R16_NI : kn >= 0;
+        const float bn = b[has ? kn : k];
+        const float xk = readlane_f(w, k & 15) * inv;
+        w = fmaf(-lv, xk, w);
+        if (t == 0) w = has ? bn : 0.f;
+        if (lane == (k & 15)) b[k] = xk;
+    }
+    wave_sync();
+}
+
 // NT threads per sample (256 / 512 / 1024): SUB = NT / 64 threads share one coarse square of the
 // prolongation (nc = 8: 64 squares; nc = 4 uses 16 of them), so a wider workgroup has more waves in flight
 // over the 4095 fine nodes; the factorisation stays in wave 0.
+template <int NC>
+constexpr int rom_fast_factor_floats() {
+    return NC == 16 ? R16_LR + R16_LC : (NC - 1) * (NC + 1) * KINV_P;
+}
+
 template <int NC, int NT>
 __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D) {
     constexpr int W = NC, BW = NC - 1, NI = (NC - 1) * (NC + 1), NN = (NC + 1) * (NC + 1), NT2 = 2 * NC * NC;
@@ -546,9 +697,9 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
     float* b = u + NN;                // [NI]
     float* lam = b + NI;              // [NN]
     float* dinv = lam + NN;           // [NI]
-    float* kinv = dinv + NI;          // [NI][KINV_P]: Z = L^{-1}
-    float* part = kinv + NI * KINV_P; // [64 NW + 64] kinv_apply scratch
-    double* du = (double*)(sm + ((NT2 + NI * W + 2 * NN + 2 * NI + NI * KINV_P + 64 * NW + 64 + 1) & ~1));   // [NN]
+    float* kinv = dinv + NI;          // [NI][KINV_P]: Z = L^{-1} (NC = 16: Lr, then Lc of chol16_wave)
+    float* part = kinv + rom_fast_factor_floats<NC>(); // [64 NW + 64] kinv_apply scratch
+    double* du = (double*)(sm + ((NT2 + NI * W + 2 * NN + 2 * NI + rom_fast_factor_floats<NC>() + 64 * NW + 64 + 1) & ~1));   // [NN]
     double* lred = du + NN;           // [NW]
     const int s = blockIdx.x;
     const int tid = threadIdx.x;
@@ -613,13 +764,24 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
     // kappa and F): otherwise the compiler sinks the loads to the prolongation, a round trip there
 #pragma unroll
     for (int k = 0; k < PF; ++k) asm volatile("" : : "v"(ypf[k]), "v"(lpf[k]));
-    static_assert(NC * NC <= 64, "window per wave");
-    // every lane of wave 0: the factorisation (uniform) + forward substitution of e_lane -> Z = L^{-1}
-    if (tid < 64) chol_inv_wave<NC>(L, kinv);
-    RPHASE(6);
-    __syncthreads();
-    // interior coarse solution u_I = K^{-1} b = Z^T (Z b), in place of b
-    kinv_apply<NC, NT>(kinv, b, part, b);
+    if constexpr (NC == 16) {
+        // wave 0: band factorisation with the forward substitution of b riding along, then the back sweep
+        if (tid < 64) {
+            const Band16 A = {L, L + 1, L + BW, W};
+            chol16_wave(A, kinv, kinv + R16_LR, b);
+            RPHASE(6);
+            band_sweep16<false>(kinv, b);
+        }
+        __syncthreads();
+    } else {
+        static_assert(NC * NC <= 64, "window per wave");
+        // every lane of wave 0: the factorisation (uniform) + forward substitution of e_lane -> Z = L^{-1}
+        if (tid < 64) chol_inv_wave<NC>(L, kinv);
+        RPHASE(6);
+        __syncthreads();
+        // interior coarse solution u_I = K^{-1} b = Z^T (Z b), in place of b
+        kinv_apply<NC, NT>(kinv, b, part, b);
+    }
     RPHASE(2);
     for (int e = tid; e < NN; e += NT) {
         const int I = e % (NC + 1), J = e / (NC + 1);
@@ -744,7 +906,15 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
         b[ii] = (float)du[I + (NC + 1) * J];
     }
     __syncthreads();
-    kinv_apply<NC, NT>(kinv, b, part, b);
+    if constexpr (NC == 16) {
+        if (tid < 64) {
+            band_sweep16<true>(kinv + R16_LR, b);
+            band_sweep16<false>(kinv, b);
+        }
+        __syncthreads();
+    } else {
+        kinv_apply<NC, NT>(kinv, b, part, b);
+    }
     for (int ii = tid; ii < NI; ii += NT) {
         const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
         lam[I + (NC + 1) * J] = b[ii];
@@ -769,8 +939,64 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
 template <int NC, int NT>
 size_t rom_fast_lds() {
     constexpr int W = NC, NI = (NC - 1) * (NC + 1), NN = (NC + 1) * (NC + 1), NT2 = 2 * NC * NC, NW = NT / 64;
-    const size_t fl = ((NT2 + NI * W + 2 * NN + 2 * NI + NI * KINV_P + 64 * NW + 64 + 1) & ~1);
+    const size_t fl = ((NT2 + NI * W + 2 * NN + 2 * NI + rom_fast_factor_floats<NC>() + 64 * NW + 64 + 1) & ~1);
     return sizeof(float) * fl + sizeof(double) * (NN + NW);
+}
+
+// Coarse solutions only at nc = 16: ONE WAVE PER SAMPLE, R16C_SPW samples per workgroup (the waves never
+// talk: no workgroup barrier, so the waves past n of a ragged last workgroup simply leave).  Each wave
+// assembles its system as three diagonals, factors it with the forward substitution riding along
+// (chol16_wave, no Lc: no forward sweep follows) and runs the one back sweep.
+constexpr int R16C_SPW = 2;
+constexpr int R16C_FLOATS = 512 + 4 * 256 + R16_LR;   // kappa, diagonal / sub-diagonals / rhs, Lr (per wave)
+
+__global__ __launch_bounds__(64 * R16C_SPW) void rom16_coarse_kernel(gpi_rom_desc d) {
+    constexpr int NC = 16, NN = 289, NT2 = 512;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * R16C_SPW + (threadIdx.x >> 6);
+    if (s >= d.n) return;
+    float* kp = sm + (threadIdx.x >> 6) * R16C_FLOATS;   // [512]
+    float* dg = kp + NT2;                                 // [256] each
+    float* o1 = dg + 256;
+    float* o15 = o1 + 256;
+    float* b = o15 + 256;
+    float* Lr = b + 256;                                  // [R16_LR]
+    const float* __restrict__ F = d.F + (int64_t)s * NN;
+    bool bad = false;
+#pragma unroll
+    for (int t = lane; t < NT2; t += 64) {
+        const float xv = rom_x(d, s, t);
+        const float kv = d.input_kappa ? xv : expf(xv) + 1e-8f;
+        bad |= !(kv > 1e-12f);
+        kp[t] = kv;
+    }
+    if (bad && d.flag) atomicOr(d.flag, 1);
+    wave_sync();
+#pragma unroll
+    for (int ii = lane; ii < R16_NI; ii += 64) {
+        const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
+        const int p = I + (NC + 1) * J;
+        const float chl = c_h(kp, NC, I - 1, J), chr = c_h(kp, NC, I, J);
+        const float cvd = J > 0 ? c_v(kp, NC, I, J - 1) : 0.f;
+        const float cvu = J < NC ? c_v(kp, NC, I, J) : 0.f;
+        dg[ii] = chl + chr + cvd + cvu;
+        o1[ii] = I - 1 >= 1 ? -chl : 0.f;
+        o15[ii] = J >= 1 ? -cvd : 0.f;
+        float rhs = F[p];
+        if (I - 1 == 0) rhs += chl * F[p - 1];
+        if (I + 1 == NC) rhs += chr * F[p + 1];
+        b[ii] = rhs;
+    }
+    wave_sync();
+    const Band16 A = {dg, o1, o15, 1};
+    chol16_wave(A, Lr, nullptr, b);
+    band_sweep16<false>(Lr, b);
+    float* uc = d.uc + (int64_t)s * NN;
+    for (int e = lane; e < NN; e += 64) {
+        const int I = e % (NC + 1), J = e / (NC + 1);
+        uc[e] = (I == 0 || I == NC) ? F[e] : b[J * (NC - 1) + (I - 1)];
+    }
 }
 
 // Coarse solutions only (FORWARD without mu_y: the VO MC predictive, N_vo x N_mc samples), nc = 4 / 8:
@@ -1164,7 +1390,7 @@ extern "C" int gpi_rom_fit(const gpi_rom_fit_desc* d, void* stream) {
 }
 
 extern "C" int gpi_rom(const gpi_rom_desc* d, void* stream) {
-    if (!d || !d->x || !d->F || d->nc < 2 || d->nc > 12 || d->refine < 1 || d->n < 0) return GPI_ERR_ARG;
+    if (!d || !d->x || !d->F || d->nc < 2 || d->nc > 16 || d->refine < 1 || d->n < 0) return GPI_ERR_ARG;
     if (d->mode == GPI_ROM_LOGLIK && (!d->Y || !d->logsig_y || (!d->gacc_logsig && !d->gls_part) || !d->gx))
         return GPI_ERR_ARG;
     if (d->mode == GPI_ROM_BACKWARD && ((!d->dmu && !d->duc) || !d->gx)) return GPI_ERR_ARG;
@@ -1190,6 +1416,18 @@ extern "C" int gpi_rom(const gpi_rom_desc* d, void* stream) {
         return GPI_OK;
     }
     static const bool slow = getenv("GPI_ROM_SLOW") && atoi(getenv("GPI_ROM_SLOW"));   // A/B: the r02 kernel
+    if (d->nc == 16 && !slow) {
+        if (d->mode == GPI_ROM_FORWARD && !d->mu_y && d->uc) {
+            const dim3 grid((d->n + R16C_SPW - 1) / R16C_SPW);
+            hipLaunchKernelGGL(rom16_coarse_kernel, grid, dim3(64 * R16C_SPW), sizeof(float) * R16C_SPW * R16C_FLOATS,
+                               (hipStream_t)stream, *d);
+        } else {
+            const size_t lds_16 = rom_fast_lds<16, 512>();
+            hipLaunchKernelGGL((rom_kernel_fast<16, 512>), dim3(d->n), dim3(512), lds_16, (hipStream_t)stream, *d, D);
+        }
+        GPI_CHECK_LAUNCH();
+        return GPI_OK;
+    }
     if ((d->nc == 8 || d->nc == 4) && !slow) {
         // nc = 8: the workgroup width (GPI_ROM_FAST_NT = 256 / 512 / 1024; r03 A/B in DESIGN.md)
         static const int fnt = getenv("GPI_ROM_FAST_NT") ? atoi(getenv("GPI_ROM_FAST_NT")) : GPI_ROM_FAST_NT_DEFAULT;

@@ -1133,7 +1133,11 @@ extern "C" int gpi_vo_moments(const gpi_vo_moments_desc* d, void* stream) {
     if (!grid_of(d->nc * d->refine, d->nc, G)) return GPI_ERR_ARG;
     if (d->n == 0) return GPI_OK;
     const size_t lds = sizeof(float) * MOM_CH * G.nn_c;
-    if (lds > 64 * 1024) return GPI_ERR_UNSUPPORTED;
+    if (lds > 160 * 1024) return GPI_ERR_UNSUPPORTED;
+    // past 64 KiB (nc = 16: 64 x 289 floats = 72.25 KiB) the kernel has to be told
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)vo_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return GPI_ERR_LAUNCH;
     hipLaunchKernelGGL(vo_moments_kernel, dim3((G.dy + 255) / 256, d->n), dim3(256), lds, (hipStream_t)stream, *d,
                        G);
     GPI_CHECK_LAUNCH();

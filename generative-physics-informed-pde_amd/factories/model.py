@@ -46,7 +46,8 @@ class ModelFactory(object):
 
     @classmethod
     def FromIdentifier(cls, identifier, *args, **kwargs):
-        classes = {c.__name__: c for c in (highres, highres32, highres128, highres256)}
+        classes = {c.__name__: c for c in (highres, highres32, highres128, highres256, highres128_rom16,
+                                           highres256_rom16)}
         return classes[identifier](*args, **kwargs)
 
     @property
@@ -157,4 +158,26 @@ class highres256(ModelFactory):
         self.params.update(ptype='NDP', dim_latent=64, dtype='float32', device='best', nx_rom=8, ny_rom=8,
                            eff_property_map_hidden_layers=0, num_refines=5, droprate=0.2)
         self._identifier = 'highres256'
+        self.set(kwargs)
+
+
+class highres128_rom16(highres128):
+    """128 x 128 with a 16 x 16 coarse-grained model (3 refinements: a coarse cell covers 8 x 8 pixels
+    instead of 16 x 16); the codec is highres128's, so every conv launch keeps its compile-time shape."""
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        self.params.update(nx_rom=16, ny_rom=16, num_refines=3)
+        self._identifier = 'highres128_rom16'
+        self.set(kwargs)
+
+
+class highres256_rom16(highres256):
+    """256 x 256 with a 16 x 16 coarse-grained model (4 refinements: 16 x 16 pixels per coarse cell
+    instead of 32 x 32); the codec is highres256's."""
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        self.params.update(nx_rom=16, ny_rom=16, num_refines=4)
+        self._identifier = 'highres256_rom16'
         self.set(kwargs)

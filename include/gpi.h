@@ -205,6 +205,9 @@ typedef struct gpi_gemm_item {
  * system equals ROM.py's row-replaced system), banded Cholesky per sample,
  * P1 prolongation to the fine free nodes, optional fused Gaussian
  * log-likelihood and its adjoint.
+ * 2 <= nc <= 16 (GPI_ERR_ARG otherwise): nc = 4, 8 and 16 have native forms (16: the band factorisation
+ * and the sweeps by one wave with the window distributed over its lanes), every other size the generic
+ * barrier-per-step kernel, which GPI_ROM_SLOW=1 (read once per process) also selects at nc = 4, 8, 16.
  * Replaces ROM.__call__/GetStiffness/_solve_eqs (bottleneck/ROM.py:59-100),
  * ReducedOrderModelOperator.forward (components.py:296-302) and
  * DiagonalGaussianLogLikelihood(Y, mu_y, 2 logsigma_y) (generative.py:473). */

@@ -40,7 +40,7 @@ def OptimizeEffectiveProperties(dataset, g, num_iterations=300, lr=1e-2, verbose
     the prediction of the last iteration (before its update), the objective of every iteration and the
     batched relative error at iterations 100, 200, ... (of the prediction made one iteration earlier).
 
-    nc = 4 / 8 without a y_preprocessor: one gpi_rom_fit launch (gpi/romfit.py).  Otherwise the same
+    nc = 4 / 8 / 16 without a y_preprocessor: one gpi_rom_fit launch (gpi/romfit.py).  Otherwise the same
     loop through g.forward_mean (gpi_rom) and torch.optim.Adam on the device."""
     Y = dataset.get('Y')
     F_ROM_BC = dataset.get('F_ROM_BC')

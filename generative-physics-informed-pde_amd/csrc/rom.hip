@@ -18,7 +18,8 @@
 //   * nc = 4 / 8: rom_kernel_fast (Z = L^{-1} by one wave) and rom_lane_kernel; nc = 16: rom_kernel_fast<16> with
 //     the factorisation and the band sweeps by one wave whose lanes share the window (chol16_wave, band_sweep16)
 //     and rom16_coarse_kernel; any other nc <= 16, and GPI_ROM_SLOW=1: the barrier-per-step rom_kernel;
-//   * gpi_rom_fit (rom_fit_kernel, below): OptimizeEffectiveProperties' whole Adam loop over x in one launch.
+//   * gpi_rom_fit (rom_fit_kernel, rom_fit16_kernel, below): OptimizeEffectiveProperties' whole Adam loop over x
+//     in one launch.
 #include "common.h"
 #include <stdlib.h>
 
@@ -1361,6 +1362,209 @@ __global__ __launch_bounds__(64) void rom_fit_kernel(gpi_rom_fit_desc d, double 
     if (bad && d.flag) atomicOr(d.flag, 1);
 }
 
+// rom_fit16_kernel (gpi_rom_fit; nc = 16): the same fit on the 16 x 16 coarse mesh, ONE WAVE64 PER SAMPLE.
+// 256 squares and 512 triangles do not fit one per lane, and the 255-unknown system has no Z = L^{-1} image:
+//   setup      lane owns squares q = lane + 64 k (k = 0..3, in that order: c_n's partial is one chain per
+//              lane); the per-square sums are staged over Lr / Lc, which are free until the first iteration.
+//   iteration  kappa -> the three diagonals and the right-hand side of rom16_coarse_kernel -> chol16_wave
+//              (forward substitution riding along) -> back sweep = u -> the fp64 block of rom_fit_kernel
+//              -> forward sweep over Lc, back sweep over Lr = lambda -> edge formula, adam_element.
+// x, m, v: 8 triangles per lane in registers (t = lane + 64 k).  Every LDS hand-off between lanes is
+// followed by wave_sync() (the workgroup is one wave).
+struct RomFit16Lds {   // float offsets after the fp64 block (every block a multiple of 4 floats)
+    static constexpr int NN = 289, NNP = 292, NT2 = 512;
+    static constexpr int ND = 5 * NN + 1;                        // doubles: G [4][NN], b [NN]
+    static constexpr int KP = 0, DG = KP + NT2, O1 = DG + 256, O15 = O1 + 256, B = O15 + 256, U = B + 256,
+                         LAM = U + NNP, FS = LAM + NNP, LR = FS + NNP, LC = LR + R16_LR, END = LC + R16_LC;
+    static constexpr size_t bytes = sizeof(double) * ND + sizeof(float) * END;
+    static_assert(sizeof(double) * 13 * 256 <= sizeof(float) * (R16_LR + R16_LC), "setup partials fit in Lr / Lc");
+    static_assert(LR % 2 == 0, "the fp64 staging area over Lr is 8-byte aligned");
+    static_assert(bytes <= 64 * 1024, "within the default dynamic-LDS limit");
+};
+
+__global__ __launch_bounds__(64) void rom_fit16_kernel(gpi_rom_fit_desc d, double gscale) {
+    using S = RomFit16Lds;
+    constexpr int NC = 16, NN = S::NN, NT2 = S::NT2, NQ = NC * NC, KX = NT2 / 64, KQ = NQ / 64;
+    extern __shared__ __attribute__((aligned(16))) double smd[];
+    double* G = smd;                   // [4][NN]: (p,p), (p,p+1), (p,p+nc+1), (p,p+nc+2)
+    double* bn = G + 4 * NN;           // [NN] W^T Y
+    float* sm = (float*)(smd + S::ND);
+    float* kp = sm + S::KP;            // [NT2] kappa
+    float* dg = sm + S::DG;            // [256] each: diagonal, 1st / 15th sub-diagonal (Band16, stride 1)
+    float* o1 = sm + S::O1;
+    float* o15 = sm + S::O15;
+    float* b = sm + S::B;              // [256] right-hand side / solution of the interior system
+    float* u = sm + S::U;              // [NN] coarse solution
+    float* lam = sm + S::LAM;          // [NN] adjoint (0 on the Dirichlet nodes)
+    float* Fs = sm + S::FS;            // [NN] F_ROM_BC
+    float* Lr = sm + S::LR;            // [R16_LR]; with Lc the setup's per-square sums before
+    float* Lc = sm + S::LC;            // [R16_LC]
+    const int lane = threadIdx.x;
+    const int64_t s = blockIdx.x;
+    const int r = d.refine, nf = NC * r;
+    const int64_t dy = (int64_t)(nf + 1) * (nf - 1);
+
+    // ---- setup: b = W^T Y, c = |Y|^2, G = W^T W (fp64, fixed order)
+    for (int e = lane; e < NN; e += 64) Fs[e] = d.F[s * NN + e];
+    double cc = 0.0;
+    {
+        double* sq = (double*)Lr;      // [NQ][13]
+        const double rinv = 1.0 / (double)r;
+        for (int k = 0; k < KQ; ++k) {
+            const int q = lane + 64 * k;
+            double pb[4] = {0.0, 0.0, 0.0, 0.0};
+            double pg[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // 00 11 22 33 01 02 03 13 23
+            const int I = q % NC, J = q / NC;
+            const int i0 = I == 0 ? 1 : I * r, i1 = (I + 1) * r - 1;     // free columns (inclusive)
+            const int rows = J == NC - 1 ? r + 1 : r;
+            for (int jj = 0; jj < rows; ++jj) {
+                const float* yrow = d.Y + s * dy + (int64_t)(J * r + jj) * (nf - 1) - 1;
+                const double eta = (double)jj * rinv;
+                for (int i = i0; i <= i1; ++i) {
+                    const double y = (double)yrow[i];
+                    const double xi = (double)(i - I * r) * rinv;
+                    double w0, w1, w2, w3;                               // corners v0, +x, +y, +x+y
+                    if (xi >= eta) { w0 = 1.0 - xi; w1 = xi - eta; w2 = 0.0; w3 = eta; }
+                    else { w0 = 1.0 - eta; w1 = 0.0; w2 = eta - xi; w3 = xi; }
+                    cc = fma(y, y, cc);
+                    pb[0] = fma(w0, y, pb[0]); pb[1] = fma(w1, y, pb[1]);
+                    pb[2] = fma(w2, y, pb[2]); pb[3] = fma(w3, y, pb[3]);
+                    pg[0] = fma(w0, w0, pg[0]); pg[1] = fma(w1, w1, pg[1]);
+                    pg[2] = fma(w2, w2, pg[2]); pg[3] = fma(w3, w3, pg[3]);
+                    pg[4] = fma(w0, w1, pg[4]); pg[5] = fma(w0, w2, pg[5]); pg[6] = fma(w0, w3, pg[6]);
+                    pg[7] = fma(w1, w3, pg[7]); pg[8] = fma(w2, w3, pg[8]);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) sq[q * 13 + c] = pb[c];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) sq[q * 13 + 4 + c] = pg[c];
+        }
+        cc = wave_sum_d(cc);
+        wave_sync();
+        for (int e = lane; e < NN; e += 64) {
+            const int I = e % (NC + 1), J = e / (NC + 1);
+            // the squares that hold node e, as their corner 3, 2, 1, 0
+            const int q3 = (I - 1) + NC * (J - 1), q2 = I + NC * (J - 1), q1 = (I - 1) + NC * J, q0 = I + NC * J;
+            const bool h3 = I > 0 && J > 0, h2 = I < NC && J > 0, h1 = I > 0 && J < NC, h0 = I < NC && J < NC;
+            double bb = 0.0, gd = 0.0, gx = 0.0, gy = 0.0, gxy = 0.0;
+            if (h3) { bb += sq[q3 * 13 + 3]; gd += sq[q3 * 13 + 4 + 3]; }
+            if (h2) { bb += sq[q2 * 13 + 2]; gd += sq[q2 * 13 + 4 + 2]; gx += sq[q2 * 13 + 4 + 8]; }
+            if (h1) { bb += sq[q1 * 13 + 1]; gd += sq[q1 * 13 + 4 + 1]; gy += sq[q1 * 13 + 4 + 7]; }
+            if (h0) {
+                bb += sq[q0 * 13 + 0]; gd += sq[q0 * 13 + 4 + 0]; gx += sq[q0 * 13 + 4 + 4];
+                gy += sq[q0 * 13 + 4 + 5]; gxy = sq[q0 * 13 + 4 + 6];
+            }
+            bn[e] = bb;
+            G[e] = gd; G[NN + e] = gx; G[2 * NN + e] = gy; G[3 * NN + e] = gxy;
+        }
+        wave_sync();                   // Lr / Lc are free from here on
+    }
+    if (lane == 0 && d.ynorm2) d.ynorm2[s] = cc;
+    if (d.iters <= 0) return;
+
+    float xr[KX], mr[KX], vr[KX];
+#pragma unroll
+    for (int k = 0; k < KX; ++k) {
+        const int t = lane + 64 * k;
+        xr[k] = d.x[s * d.x_stride + t];
+        mr[k] = d.m ? d.m[s * NT2 + t] : 0.f;
+        vr[k] = d.v ? d.v[s * NT2 + t] : 0.f;
+    }
+    bool bad = false;
+    const Band16 A = {dg, o1, o15, 1};
+    for (int it = 0; it < d.iters; ++it) {
+        const bool last = it == d.iters - 1;
+#pragma unroll
+        for (int k = 0; k < KX; ++k) {
+            const int t = lane + 64 * k;
+            const float kv = expf(xr[k]) + 1e-8f;
+            bad |= !(kv > 1e-12f);
+            kp[t] = kv;
+            if (last && d.x_eval) d.x_eval[s * NT2 + t] = xr[k];
+        }
+        wave_sync();
+        // ---- the interior system as three diagonals + rhs, as rom16_coarse_kernel
+#pragma unroll
+        for (int ii = lane; ii < R16_NI; ii += 64) {
+            const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
+            const int p = I + (NC + 1) * J;
+            const float chl = c_h(kp, NC, I - 1, J), chr = c_h(kp, NC, I, J);
+            const float cvd = J > 0 ? c_v(kp, NC, I, J - 1) : 0.f;
+            const float cvu = J < NC ? c_v(kp, NC, I, J) : 0.f;
+            dg[ii] = chl + chr + cvd + cvu;
+            o1[ii] = I - 1 >= 1 ? -chl : 0.f;
+            o15[ii] = J >= 1 ? -cvd : 0.f;
+            float rhs = Fs[p];
+            if (I - 1 == 0) rhs += chl * Fs[p - 1];
+            if (I + 1 == NC) rhs += chr * Fs[p + 1];
+            b[ii] = rhs;
+        }
+        wave_sync();
+        chol16_wave(A, Lr, Lc, b);
+        band_sweep16<false>(Lr, b);
+        for (int e = lane; e < NN; e += 64) {
+            const int I = e % (NC + 1), J = e / (NC + 1);
+            const float ue = (I == 0 || I == NC) ? Fs[e] : b[J * (NC - 1) + (I - 1)];
+            u[e] = ue;
+            if (last && d.uc) d.uc[s * NN + e] = ue;
+        }
+        wave_sync();
+        // ---- fp64: G u, the squared residual and its gradient
+        double ssp = 0.0;
+        for (int e = lane; e < NN; e += 64) {
+            const int I = e % (NC + 1), J = e / (NC + 1);
+            double gu = G[e] * (double)u[e];
+            if (I > 0) gu = fma(G[NN + e - 1], (double)u[e - 1], gu);
+            if (I < NC) gu = fma(G[NN + e], (double)u[e + 1], gu);
+            if (J > 0) gu = fma(G[2 * NN + e - (NC + 1)], (double)u[e - (NC + 1)], gu);
+            if (J < NC) gu = fma(G[2 * NN + e], (double)u[e + (NC + 1)], gu);
+            if (I > 0 && J > 0) gu = fma(G[3 * NN + e - (NC + 2)], (double)u[e - (NC + 2)], gu);
+            if (I < NC && J < NC) gu = fma(G[3 * NN + e], (double)u[e + (NC + 2)], gu);
+            ssp = fma((double)u[e], gu - 2.0 * bn[e], ssp);
+            if (I > 0 && I < NC) b[J * (NC - 1) + (I - 1)] = (float)(gscale * (gu - bn[e]));
+        }
+        const double ss = wave_sum_d(ssp) + cc;
+        bad |= !(fabs(ss) <= 1.7976931348623157e308);
+        if (lane == 0 && d.sumsq) d.sumsq[(int64_t)it * d.n + s] = ss;
+        wave_sync();
+        // ---- adjoint lambda = K^{-1} g_u (interior), dJ/dx per coarse triangle, Adam
+        band_sweep16<true>(Lc, b);
+        band_sweep16<false>(Lr, b);
+        for (int e = lane; e < NN; e += 64) {
+            const int I = e % (NC + 1), J = e / (NC + 1);
+            lam[e] = (I == 0 || I == NC) ? 0.f : b[J * (NC - 1) + (I - 1)];
+        }
+        wave_sync();
+        const int64_t step = d.step0 + it + 1;
+        const double bc1 = 1.0 - pow((double)d.beta1, (double)step);
+        const double bc2 = 1.0 - pow((double)d.beta2, (double)step);
+        const float step_size = (float)((double)d.lr / bc1);
+        const float bc2_sqrt = (float)sqrt(bc2);
+#pragma unroll
+        for (int k = 0; k < KX; ++k) {
+            const int t = lane + 64 * k;
+            const int q = t >> 1, ul = t & 1;
+            const int I = q % NC, J = q / NC;
+            const int v0 = I + (NC + 1) * J, v1 = v0 + 1, v2 = v0 + (NC + 1), v3 = v2 + 1;
+            float dk;
+            if (!ul) dk = -(lam[v0] - lam[v1]) * (u[v0] - u[v1]) - (lam[v1] - lam[v3]) * (u[v1] - u[v3]);
+            else dk = -(lam[v2] - lam[v3]) * (u[v2] - u[v3]) - (lam[v0] - lam[v2]) * (u[v0] - u[v2]);
+            const float g = 0.5f * dk * (kp[t] - 1e-8f);
+            adam_element(g, xr[k], mr[k], vr[k], d.beta1, d.beta2, d.eps, step_size, bc2_sqrt);
+        }
+        wave_sync();                   // kp, u, lam, b are rewritten by the next iteration
+    }
+#pragma unroll
+    for (int k = 0; k < KX; ++k) {
+        const int t = lane + 64 * k;
+        d.x[s * d.x_stride + t] = xr[k];
+        if (d.m) d.m[s * NT2 + t] = mr[k];
+        if (d.v) d.v[s * NT2 + t] = vr[k];
+    }
+    if (bad && d.flag) atomicOr(d.flag, 1);
+}
+
 }  // namespace
 
 #ifdef GPI_PHASE_TIMING
@@ -1375,13 +1579,15 @@ extern "C" int gpi_debug_rom_stamps(unsigned long long* out) {
 
 extern "C" int gpi_rom_fit(const gpi_rom_fit_desc* d, void* stream) {
     if (!d || d->nc < 2 || d->refine < 1 || d->n < 0 || d->iters < 0 || d->n_total < 0 || d->step0 < 0) return GPI_ERR_ARG;
-    if ((d->nc != 4 && d->nc != 8) || (int64_t)d->nc * d->refine > 4096) return GPI_ERR_UNSUPPORTED;
+    if ((d->nc != 4 && d->nc != 8 && d->nc != 16) || (int64_t)d->nc * d->refine > 4096) return GPI_ERR_UNSUPPORTED;
     if (d->n == 0) return GPI_OK;
     if (!d->Y || !d->F || !d->x || d->x_stride < 2 * d->nc * d->nc || !d->m != !d->v) return GPI_ERR_ARG;
     const int64_t nf = (int64_t)d->nc * d->refine, dy = (nf + 1) * (nf - 1);
     // d/du of the MSE mean: 2 / (n_total d_y) (G u - b)
     const double gscale = 2.0 / ((double)(d->n_total ? d->n_total : d->n) * (double)dy);
-    if (d->nc == 8)
+    if (d->nc == 16)
+        hipLaunchKernelGGL(rom_fit16_kernel, dim3(d->n), dim3(64), RomFit16Lds::bytes, (hipStream_t)stream, *d, gscale);
+    else if (d->nc == 8)
         hipLaunchKernelGGL(rom_fit_kernel<8>, dim3(d->n), dim3(64), RomFitLds<8>::bytes, (hipStream_t)stream, *d, gscale);
     else
         hipLaunchKernelGGL(rom_fit_kernel<4>, dim3(d->n), dim3(64), RomFitLds<4>::bytes, (hipStream_t)stream, *d, gscale);

@@ -5,6 +5,9 @@ fit_effective_properties() runs every Adam iteration of the reference's Optimize
 J = MSELoss(forward_mean(x, F), Y) over x, one wave per sample, the fine grid read once
 (|W u - Y|^2 = u^T G u - 2 b^T u + c with G = W^T W, b = W^T Y, c = |Y|^2 in fp64).  No host
 synchronisation here; the records stay on the device until the caller reads them.
+
+Coarse meshes: nc = 4, 8 (rom_fit_kernel) and 16 (rom_fit16_kernel: the band factor and three sweeps per
+iteration).  Any other nc raises NativeError (GPI_ERR_UNSUPPORTED); nothing falls back to a host loop here.
 """
 import ctypes as C
 
@@ -12,7 +15,7 @@ import torch
 
 from . import _lib as L
 
-SUPPORTED_NC = (4, 8)
+SUPPORTED_NC = (4, 8, 16)
 
 
 class RomFitState(object):
@@ -55,7 +58,8 @@ def fit_effective_properties(Y, F, nc, refine, num_iterations, lr=1e-2, betas=(0
                              state=None, n_total=None):
     """num_iterations Adam steps on x [N, 2 nc^2] (from x0, or zeros) against the labels Y [N, d_y] with
     the ROM right-hand sides F [N, (nc+1)^2].  state continues an earlier fit of the same rows; n_total is
-    the N of the MSE mean (default: Y's rows; give the full count when fitting a part of a batch)."""
+    the N of the MSE mean (default: Y's rows; give the full count when fitting a part of a batch).
+    nc in SUPPORTED_NC (4, 8, 16)."""
     for t in (Y, F):
         L.require_device(t)
     nc, refine, T = int(nc), int(refine), int(num_iterations)

@@ -255,8 +255,10 @@ typedef struct gpi_rom_desc {
  * -> adjoint solve with the same factor -> dJ/dx by gpi_rom's edge formula -> torch's Adam update
  * (adam_element, bias corrections of step step0 + i + 1).  Results depend on nothing but the sample's
  * own rows and the scalars: any split of the batch (with n_total fixed) or of the iterations (with
- * m, v, step0 carried over) gives the same bits.  nc = 4 and 8 (GPI_ERR_UNSUPPORTED otherwise), any
- * refine >= 1 with nc refine <= 4096.  n = 0 launches nothing. */
+ * m, v, step0 carried over) gives the same bits.  nc = 4, 8 and 16 (GPI_ERR_UNSUPPORTED otherwise, with
+ * every buffer untouched), any refine >= 1 with nc refine <= 4096.  nc = 16 keeps the band factor itself
+ * (gpi_rom's wave factorisation and band sweeps: one factorisation and three sweeps per iteration) where
+ * nc = 4 / 8 hold L^{-1}.  n = 0 launches nothing. */
 typedef struct gpi_rom_fit_desc {
     int32_t nc, refine, n, iters;
     int64_t n_total;           /* the N of the MSE mean; 0: n */

@@ -6,15 +6,18 @@ after a warm-up fit per shape and arm; reported: median (min..max) over `--repea
   B  the module-path loop a user writes without it: RomOperatorFunction (gpi_rom FORWARD + BACKWARD) +
      mse_loss + torch.optim.Adam, T host-launched iterations
 Shapes: 64 x 64 (nc = 8) with N = 32 and N = 2048; 128 x 128 (nc = 8) N = 512; 256 x 256 (nc = 8) N = 128;
-32 x 32 (nc = 4) N = 128.
+32 x 32 (nc = 4) N = 128.  --set nc16: the 16 x 16 coarse mesh, 128 x 128 (refine 8) with N = 32 and N = 512,
+256 x 256 (refine 16) N = 128, written to profiles/romfit16_bench.json.
 
 Also reported from the shapes: the bytes arm A has to move (Y once, F, x / m / v in and out, the records) and
 the useful flops of one iteration of one sample (band Cholesky, the 63 forward substitutions that form
-Z = L^{-1}, four triangular mat-vecs, the 7-point fp64 G u), which give the achieved bandwidth and flop rate
+Z = L^{-1}, four triangular mat-vecs, the 7-point fp64 G u; nc = 16: band Cholesky with the forward
+substitution riding along and three band sweeps instead), which give the achieved bandwidth and flop rate
 next to the time of one iteration of one wave -- the fit is a chain of dependent steps inside each wave
 (latency-bound), not a bandwidth or throughput problem.
 
     python tools/romfit_bench.py --out profiles/romfit_bench.json
+    python tools/romfit_bench.py --set nc16
 """
 import argparse
 import json
@@ -26,7 +29,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'generative-physics-informed-pde_amd'))
 
-SHAPES = [(64, 8, 32), (64, 8, 2048), (128, 8, 512), (256, 8, 128), (32, 4, 128)]   # (n_fine, nc, N)
+SHAPES = {'nc8': [(64, 8, 32), (64, 8, 2048), (128, 8, 512), (256, 8, 128), (32, 4, 128)],   # (n_fine, nc, N)
+          'nc16': [(128, 16, 32), (128, 16, 512), (256, 16, 128)]}
+OUT = {'nc8': 'romfit_bench.json', 'nc16': 'romfit16_bench.json'}
 
 
 def summary(xs):
@@ -40,6 +45,8 @@ def algorithmic(n, nc, N, T):
     chol = ni * (bw + bw * (bw + 1))                    # scale the column, rank-1 update of the window (fma = 2)
     zform = 2 * bw * ni * (ni + 1) // 2                 # forward substitution of e_j, j < NI
     matvec = 4 * ni * (ni + 1)                          # four triangular mat-vecs, fma = 2
+    if nc == 16:                                        # no Z: four band substitutions (one inside the factorisation)
+        zform, matvec = 0, 4 * ni * (2 * bw + 1)
     rest = 2 * 7 * nn + 3 * nn + 12 * nt + 20 * nt      # G u and ss (fp64), the edge formula, exp + Adam
     return nbytes, chol + zform + matvec + rest
 
@@ -49,8 +56,10 @@ def main():
     ap.add_argument('--iters', type=int, default=300)
     ap.add_argument('--lr', type=float, default=1e-2)
     ap.add_argument('--repeats', type=int, default=9)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'romfit_bench.json'))
+    ap.add_argument('--set', choices=sorted(SHAPES), default='nc8')
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', OUT[a.set])
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -70,7 +79,7 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1)
 
-    for n, nc, N in SHAPES:
+    for n, nc, N in SHAPES[a.set]:
         r = n // nc
         rng = np.random.default_rng(n + N)
         mc = fem.unit_square_mesh(nc)

@@ -4,8 +4,9 @@
 // `th` whole output rows of ONE sample, so every (channel, tile) operand is a
 // single contiguous run of global memory whose cache lines are used whole.
 // Operands live in LDS as row images with a zero halo of HALO columns on each
-// side (pitch = width + 2 HALO), filled by 16-byte LDS-DMA (global_load_lds);
-// halo chunks and rows outside the plane read a zero page.  A workgroup runs
+// side (pitch = width + 2 HALO), filled by 16-byte buffer LDS-DMA (buffer_load ...
+// lds through one descriptor per operand); halo chunks and rows outside the plane
+// take an out-of-range offset, which the hardware turns into zeros.  A workgroup runs
 // in four phases so that it pays ONE global round trip before it computes:
 //   1. issue every global read at once: the LDS images (input, output
 //      gradient, BN-backward operand), the weights, the 16 replicas of the BN
@@ -44,8 +45,8 @@ namespace {
 
 constexpr int HALO = 4;   // zero halo columns on each side of an LDS row image
 
-// 256 zero bytes in device memory: the source of LDS-DMA padding lanes and of
-// the stat loads of unused lanes.
+// 256 zero bytes in device memory: the source of the register operand loads'
+// padding lanes and of the stat loads of unused lanes.
 __device__ __attribute__((aligned(256))) float g_zero_page[64];
 
 // q = e / d without a division: e * d < 2^32 (checked on the host).
@@ -509,26 +510,41 @@ __device__ __forceinline__ void fold_shape(gpi_conv_desc& d, ConvGeom& G) {
     }
 }
 
-__device__ __forceinline__ void glds4(const float* g, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
+// Buffer descriptor over `bytes` bytes at `base` (raw buffer: stride 0, num_records in bytes).  Built from
+// wave-uniform values made provably so (readfirstlane), or the compiler wraps every access through it in a
+// loop over the distinct descriptors of the wave.  A buffer LDS-DMA load whose byte offset is >= bytes
+// fetches nothing and writes ZERO to its LDS slot (gpi_debug_buffer_lds_probe; tests/test_gpu_conv_staging.py),
+// so padding needs no zero page and no 64-bit pointer per lane: it is the 32-bit offset BUF_OOR.
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+constexpr int BUF_OOR = (int)0x80000000u;   // >= every num_records below (all < 2^31), also with the access size added
+__device__ __forceinline__ rsrc_t make_rsrc(const float* base, int bytes) {
+    const uint64_t a = (uint64_t)base;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0,
+                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+__device__ __forceinline__ void blds4(rsrc_t r, int byte_off, float* lds_wave_base) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 4, byte_off, 0,
+                                             0, 0);
+}
+__device__ __forceinline__ void blds16(rsrc_t r, int byte_off, float* lds_wave_base) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, byte_off,
+                                             0, 0, 0);
 }
 
-__device__ __forceinline__ void glds16(const float* g, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// dst[e] = *src(e) for e in [0, total) by 4-byte LDS-DMA; src(e) == nullptr reads the
-// zero page.  dst is padded to a multiple of 256 floats (whole waves write).
+// dst[e] = base[src(e)] for e in [0, total) by 4-byte buffer LDS-DMA over the n floats at base; src(e) < 0
+// stages a zero.  dst is padded to a multiple of 256 floats (whole waves write).
 template <typename Src>
-__device__ __forceinline__ void stage(float* dst, int total, const float* zero, Src src) {
-    const int wb = threadIdx.x & ~63;
+__device__ __forceinline__ void stage(float* dst, int total, const float* base, int n, Src src) {
+    // (the wave's first element as a scalar: the per-step test is a scalar branch and the LDS base needs no lane)
+    const int wb = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63);
+    const rsrc_t rs = make_rsrc(base, 4 * n);
     for (int e0 = 0; e0 < total; e0 += 256) {
         if (e0 + wb < total) {
             const int e = e0 + (int)threadIdx.x;
-            const float* p = e < total ? src(e) : nullptr;
-            glds4(p ? p : zero, dst + e0 + wb);
+            const int o = e < total ? src(e) : -1;
+            blds4(rs, o >= 0 ? 4 * o : BUF_OOR, dst + e0 + wb);
         }
     }
 }
@@ -558,28 +574,26 @@ struct ChunkIter {
 constexpr int IMG_MARGIN4 = 16;
 __host__ __device__ inline int img_floats(int nq, int nr, int P) { return pad256(4 * (nq * nr * (P / 4) + IMG_MARGIN4)); }
 
-// Row image of nq planes (plane q at plane(q), an h x w plane): rows [r0, r0 + nr),
-// LDS pitch P = w + 2 HALO.  16-byte LDS-DMA; halo chunks, rows outside [0, h) and the
-// IMG_MARGIN4 tail chunks read the zero page.
-template <typename Plane>
+// Row image of the nq planes at base (h x w planes, contiguous: plane q at base + q h w; wave-uniform):
+// rows [r0, r0 + nr), LDS pitch P = w + 2 HALO.  16-byte buffer LDS-DMA through one descriptor over the nq
+// planes; halo chunks, rows outside [0, h) and the IMG_MARGIN4 tail chunks take the out-of-range offset and
+// land as zeros.  A chunk of a plane q >= nq (the tail of the last step) with an in-plane row and column is
+// out of range by its own offset, q h w >= nq h w.
 __device__ __forceinline__ void stage_img(float* dst, int nq, int nr, int P, Div d_q4, Div d_p4, int sq, int sr,
-                                          int sc, int r0, int h, int w, const float* zero, Plane plane) {
+                                          int sc, int r0, int h, int w, const float* base) {
     const int P4 = P >> 2, plane4 = nr * P4, total = nq * plane4 + IMG_MARGIN4;
-    const int wb = threadIdx.x & ~63;
-    const int c4lo = HALO / 4, c4hi = HALO / 4 + w / 4;
+    // (the wave's first element as a scalar: the per-step test is a scalar branch and the LDS base needs no lane)
+    const int wb = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63);
+    const int c4lo = HALO / 4, hw = h * w;
+    const rsrc_t rs = make_rsrc(base, 4 * nq * hw);
     ChunkIter it;
     it.init(threadIdx.x, plane4, P4, d_q4, d_p4);
     for (int e0 = 0; e0 < total; e0 += 256) {
         if (e0 + wb < total) {
-            const int row = r0 + it.r;
-            const bool ok = it.q < nq && row >= 0 && row < h && it.c4 >= c4lo && it.c4 < c4hi;
-            // the chunk's plane address computed for every lane (never dereferenced where !ok), then ONE select:
-            // without the empty asm the compiler sank the address arithmetic under three exec-masked branches
-            // (the bounds tests), ≈ 10 SALU + branch issue per chunk in the staging loops of every conv launch
-            const float* pv = plane(it.q) + row * w + 4 * (it.c4 - c4lo);
-            asm volatile("" : "+v"(pv));
-            const float* p = ok ? pv : zero;
-            glds16(p, dst + 4 * (e0 + wb));
+            const int row = r0 + it.r, col4 = it.c4 - c4lo;
+            const bool ok = (unsigned)row < (unsigned)h && (unsigned)col4 < (unsigned)(w >> 2);
+            const int off = 4 * (it.q * hw + row * w + 4 * col4);
+            blds16(rs, ok ? off : BUF_OOR, dst + 4 * (e0 + wb));
         }
         it.step(sq, sr, sc, P4, nr);
     }
@@ -910,22 +924,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
     PHASE(1);
 
     // ---- phase 1: every global read of the tile in flight together
-    stage(wT, nw, zero, [&](int e) -> const float* {
+    stage(wT, nw, params + w_off, d.cout * d.cin * KK, [&](int e) -> int {
         if constexpr (ROWS2) {
             // slot (half, tap, j) holds channel half * ceil(cout / 2) + j: halves of ceil(cout / 2) and
             // floor(cout / 2) channels; the other slots and the padding hold zeros
             const int ci = e / WCI, q = e - ci * WCI, hf = q / WH, i = q - hf * WH, tap = i / HS, j = i - tap * HS;
             const int c2 = (d.cout + 1) >> 1;
             const bool ok = tap < KK && j < (hf ? d.cout - c2 : c2);
-            return ok ? params + w_off + ((int64_t)(hf * c2 + j) * d.cin + ci) * KK + tap : nullptr;
+            return ok ? ((hf * c2 + j) * d.cin + ci) * KK + tap : -1;
         }
         const int co = e % CP, r = e / CP;
-        return co < d.cout ? params + w_off + (int64_t)co * d.cin * KK + r : nullptr;
+        return co < d.cout ? co * d.cin * KK + r : -1;
     });
     int iy0, rh_;
     in_rows(K, S, UP, d.pad, T.oy0, Gt.th, iy0, rh_);
-    stage_img(img, d.cin, Gt.rh, Gt.P, Gt.d_in4, Gt.d_P4, Gt.in_sq, Gt.in_sr, Gt.in_sc, iy0, d.h_in, d.w_in, zero,
-              [&](int q) -> const float* { return ib + (int64_t)q * HWi; });
+    stage_img(img, d.cin, Gt.rh, Gt.P, Gt.d_in4, Gt.d_P4, Gt.in_sq, Gt.in_sr, Gt.in_sc, iy0, d.h_in, d.w_in, ib);
     // (issued after the DMA; stored to LDS only after the stat loads are issued and waited for -- an
     // LDS store of it right here would drain every outstanding DMA first: one more round trip)
     float dsv = 1.f;
@@ -1531,21 +1544,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
     if (vop) {
         // weights W[co][ci][ky][kx] transposed for the packed (v_pk_fma_f32) loops: input gradient
         // WB[((co K + ky) K + kx) CIV + ci]; FUSE forward WF[((ci K + kx) K + ky) 2 + co]
-        stage(mid, d.cout * KK * CIV, zero, [&](int e) -> const float* {
+        stage(mid, d.cout * KK * CIV, params + w_off, d.cout * d.cin * KK, [&](int e) -> int {
             const int ci = e % CIV, t = e / CIV, co = t / KK, tap = t - co * KK;
-            return ci < d.cin ? params + w_off + ((int64_t)co * d.cin + ci) * KK + tap : nullptr;
+            return ci < d.cin ? (co * d.cin + ci) * KK + tap : -1;
         });
         if (FUSE)
-            stage(mid + 256, d.cin * KK * 2, zero, [&](int e) -> const float* {
+            stage(mid + 256, d.cin * KK * 2, params + w_off, d.cout * d.cin * KK, [&](int e) -> int {
                 const int co = e & 1, t = e >> 1, ci = t / KK, r = t - ci * KK, kx = r / K, ky = r - kx * K;
-                return params + w_off + ((int64_t)co * d.cin + ci) * KK + ky * K + kx;
+                return (co * d.cin + ci) * KK + ky * K + kx;
             });
     }
     if (has_gin && dg_role && !vop)
-        stage(wD, nwd, zero, [&](int e) -> const float* {
+        stage(wD, nwd, params + w_off, d.cout * d.cin * KK, [&](int e) -> int {
             const int ci = e & 15, k = e >> 4;
             const int co = k / KK, t = k - co * KK;
-            return ci < d.cin && k < KD ? params + w_off + ((int64_t)co * d.cin + ci) * KK + t : nullptr;
+            return ci < d.cin && k < KD ? (co * d.cin + ci) * KK + t : -1;
         });
     PHASE(12);
     int gy0, gh_;
@@ -1569,8 +1582,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
             tv0[p] = *as_gld(ok ? tg + oy * d.w_out + x : zero);
         }
     } else {
-        stage_img(gl, d.cout, Gt.gh, Gt.PG, Gt.d_g4, Gt.d_PG4, Gt.g_sq, Gt.g_sr, Gt.g_sc, gy0, d.h_out, d.w_out, zero,
-                  [&](int q) -> const float* { return ws + gout_off + gbase + (int64_t)q * HWo; });
+        stage_img(gl, d.cout, Gt.gh, Gt.PG, Gt.d_g4, Gt.d_PG4, Gt.g_sq, Gt.g_sr, Gt.g_sc, gy0, d.h_out, d.w_out,
+                  ws + gout_off + gbase);
     }
     PHASE(13);
     f32x4 zr[ZREG];           // zreg: this thread's chunks tid + 256 u of the z image
@@ -1589,15 +1602,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
             it.step(Gt.g_sq, Gt.g_sr, Gt.g_sc, P4, Gt.gh);
         }
     } else if (obn) {
-        stage_img(gz, d.cout, Gt.gh, Gt.PG, Gt.d_g4, Gt.d_PG4, Gt.g_sq, Gt.g_sr, Gt.g_sc, gy0, d.h_out, d.w_out, zero,
-                  [&](int q) -> const float* { return ws + out_off + gbase + (int64_t)q * HWo; });
+        stage_img(gz, d.cout, Gt.gh, Gt.PG, Gt.d_g4, Gt.d_PG4, Gt.g_sq, Gt.g_sr, Gt.g_sc, gy0, d.h_out, d.w_out,
+                  ws + out_off + gbase);
     }
     PHASE(14);
     int iy0, rh_;
     in_rows(K, S, UP, d.pad, T.oy0, Gt.th, iy0, rh_);
     const int iyA = FUSE ? iy0 - K / 2 : iy0;        // first row of the LDS input image
-    stage_img(al, d.cin, Gt.rh, Gt.P, Gt.d_in4, Gt.d_P4, Gt.in_sq, Gt.in_sr, Gt.in_sc, iyA, d.h_in, d.w_in, zero,
-              [&](int q) -> const float* { return ib + (int64_t)q * HWi; });
+    stage_img(al, d.cin, Gt.rh, Gt.P, Gt.d_in4, Gt.d_P4, Gt.in_sq, Gt.in_sr, Gt.in_sc, iyA, d.h_in, d.w_in, ib);
     PHASE(8);
     // input-gradient epilogue operand (previous S_in, when accumulating) of this wave's first
     // four pixel blocks: lane (kq, l16) owns channel l16 at the 4 consecutive pixels
@@ -2911,6 +2923,34 @@ extern "C" int gpi_bn_running_update(const gpi_bn_running_item* items, int n_ite
     const int threads = n_items * max_channels;
     hipLaunchKernelGGL(bn_running_kernel, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, items, n_items,
                        max_channels, stats, n_stats, momentum);
+    GPI_CHECK_LAUNCH();
+    return GPI_OK;
+}
+
+// What a buffer LDS-DMA load does with an out-of-range offset (the premise of stage / stage_img): one wave
+// fills 320 LDS words with the sentinel, loads 64 x 16 bytes at byte offsets off16[lane] into words [0, 256)
+// and 64 x 4 bytes at off4[lane] into words [256, 320) through a descriptor over `bytes` bytes at src, and
+// copies the LDS words out.
+constexpr uint32_t PROBE_SENTINEL = 0xdeadbeefu;
+__global__ __launch_bounds__(64) void buffer_lds_probe_kernel(const float* src, int bytes, const int32_t* off16,
+                                                              const int32_t* off4, uint32_t* out) {
+    __shared__ __attribute__((aligned(16))) float lds[320];
+    const int lane = threadIdx.x;
+    for (int i = lane; i < 320; i += 64) lds[i] = __builtin_bit_cast(float, PROBE_SENTINEL);
+    __syncthreads();
+    const rsrc_t rs = make_rsrc(src, bytes);
+    blds16(rs, off16[lane], lds);
+    blds4(rs, off4[lane], lds + 256);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int i = lane; i < 320; i += 64) out[i] = __builtin_bit_cast(uint32_t, lds[i]);
+}
+
+extern "C" int gpi_debug_buffer_lds_probe(const float* src, int32_t bytes, const int32_t* off16, const int32_t* off4,
+                                          uint32_t* out, void* stream) {
+    if (!src || !off16 || !off4 || !out || bytes <= 0 || (bytes & 15) || ((uintptr_t)src & 15)) return GPI_ERR_ARG;
+    hipLaunchKernelGGL(buffer_lds_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, src, (int)bytes, off16, off4,
+                       out);
     GPI_CHECK_LAUNCH();
     return GPI_OK;
 }

@@ -787,6 +787,13 @@ int gpi_stream_wait_ge(const int64_t* a, const int64_t* b, uint32_t* err, void* 
  * signal arrived while the probe spun (~40 ms bound), i.e. B's kernels run past a spinning kernel of A.
  * *flag must be 0 before the pair is launched. */
 int gpi_queue_probe(const uint32_t* flag, uint32_t* seen, void* stream);
+/* Debug probe of the hardware rule the conv kernels' operand staging is built on: what a buffer LDS-DMA load
+ * writes for an out-of-range offset.  One wave fills 320 LDS words with 0xdeadbeef, then loads, through a raw
+ * buffer descriptor over `bytes` bytes at src (16-byte aligned, bytes a multiple of 16), 64 x 16 bytes at the
+ * byte offsets off16[0..64) into words [0, 256) and 64 x 4 bytes at off4[0..64) into words [256, 320), and
+ * copies the 320 LDS words to out.  Offsets >= bytes (negative ones included) are out of range. */
+int gpi_debug_buffer_lds_probe(const float* src, int32_t bytes, const int32_t* off16, const int32_t* off4,
+                               uint32_t* out, void* stream);
 
 /* Device Philox4x32-10 normals: out[i] = N(0,1) for counter (*offset + i);
  * offset is a device uint64 advanced by gpi_rng_advance (graph-replay safe). */

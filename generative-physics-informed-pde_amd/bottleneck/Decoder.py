@@ -1,9 +1,10 @@
 """CNNDecoder (reference bottleneck/Decoder.py:163-325) on the native codec.
 
 Linear latent map -> 1 x 8 x 8 image -> conv0 -> [DenseBlock -> TransitionUp]
--> last decoding -> 2 channels (mean, logsigma).  Module tree / order as in
-the reference; ``forward`` runs the latent map and the whole conv stack as
-native kernels.
+-> last decoding -> 2 channels (mean, logsigma), or with ``binary=True`` one
+logit channel followed by ``Sigmoid`` (two-phase media, reference
+Decoder.py:204-207,240-241).  Module tree / order as in the reference;
+``forward`` runs the latent map and the whole conv stack as native kernels.
 """
 import torch
 import torch.nn as nn
@@ -24,6 +25,8 @@ class BaseDecoder(lamp.modules.BaseModule):
 
     def propagate_samples(self, Z):
         """Decoder.py:29-37: a sample of the decoder's Gaussian for each z."""
+        if getattr(self, '_binary', False):
+            raise NotImplementedError('propagate_samples is defined for the Gaussian decoder only')
         means, logsigmas = self.forward(Z)
         if means.shape != logsigmas.shape:
             raise RuntimeError('Implementation assumes that full logsigmas matrix is given; check for broadcasting')
@@ -46,19 +49,21 @@ class CNNDecoder(BaseDecoder):
         if out_size != target_img_size:
             raise ValueError('Latent image size {0}x{0} with {1} blocks yields a {2}x{2} output, target is {3}x{3}'
                              .format(latent_img_size, len(blocks), out_size, target_img_size))
-        if binary or force_single_output or homoscedastic:
-            raise NotImplementedError('the native decoder implements the heteroscedastic Gaussian head '
-                                      '(binary / homoscedastic variants are not on the ELBO path)')
+        if force_single_output or homoscedastic:
+            raise NotImplementedError('the native decoder implements the heteroscedastic Gaussian head and the '
+                                      'binary (Bernoulli) head (single-output / homoscedastic variants are not '
+                                      'on the ELBO path)')
         if upsample != 'nearest':
             raise NotImplementedError('only nearest upsampling is supported')
         self._output_shape = (target_img_size, target_img_size)
         self._dim_in = dim_latent
         self._dim_out = target_img_size ** 2
-        self._binary = False
+        self._binary = bool(binary)
+        out_channels = 1 if self._binary else 2
         self._homoscedastic = False
         self._latent_img_dimension = latent_img_size ** 2 * latent_img_features
         self._cfg = dict(latent_img_size=latent_img_size, latent_img_features=latent_img_features,
-                         init_features=init_features, blocks=list(blocks), growth=growth_rate, out_channels=2,
+                         init_features=init_features, blocks=list(blocks), growth=growth_rate, out_channels=out_channels,
                          drop_rate=float(drop_rate))
         self.latent_map = nn.Linear(dim_latent, self._latent_img_dimension)
         self.features = nn.Sequential()
@@ -73,7 +78,10 @@ class CNNDecoder(BaseDecoder):
                                                                             drop_rate=drop_rate,
                                                                             upsample=upsample))
                 nf //= 2
-        self.features.add_module('LastTransUp', last_decoding(nf, 2, drop_rate=drop_rate, upsample=upsample))
+        self.features.add_module('LastTransUp', last_decoding(nf, out_channels, drop_rate=drop_rate,
+                                                              upsample=upsample))
+        if self._binary:
+            self.features.add_module('Sigmoid', nn.Sigmoid())
 
     def native_config(self):
         return dict(self._cfg)
@@ -101,6 +109,11 @@ class CNNDecoder(BaseDecoder):
     def forward(self, x, flatten=False):
         from gpi.native import decoder_forward
         out = decoder_forward(self, x)
+        if self._binary:
+            # the probability image, as the reference's Sigmoid module: the training engine returns the logit
+            # image (differentiable), the eval engine the probabilities
+            prob = torch.sigmoid(out[:, 0]) if self.training else out[:, 0]
+            return prob.reshape(prob.shape[0], -1) if flatten else prob
         mean, logsigmas = out[:, 0], out[:, 1]
         if flatten:
             mean = mean.reshape(mean.shape[0], -1)

@@ -357,7 +357,14 @@ class GenerativeModel(lamp.modules.BaseModule):
 
     def random_field_likelihood(self, predict, target):
         if not isinstance(predict, tuple):
-            raise NotImplementedError('binary fields are not on the ELBO path')
+            # binary decoder (generative.py:240-244): predict is the probability image, the batch's minimum
+            # is the low phase; summed binary cross-entropy.  (The ELBO engines score the same likelihood
+            # from the logit, GPI_EPI_BERNOULLI_LOSS; this is the torch form for direct callers.)
+            target_new = torch.ones_like(target)
+            target_new[target == target.min()] = 0
+            bs = predict.shape[0]
+            return -torch.nn.functional.binary_cross_entropy(predict.reshape(bs, -1), target_new.reshape(bs, -1),
+                                                             reduction='sum')
         if self.config['reconstruct_log_eff_property']:
             return DiagonalGaussianLogLikelihood(target, predict[0], 2 * predict[1])
         return DiagonalGaussianLogLikelihood(torch.exp(target), torch.exp(predict[0]), 2 * predict[1])

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <string.h>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 #include <atomic>
@@ -199,6 +200,10 @@ int env_int(const char* name, int dflt) {
     return v && *v ? atoi(v) : dflt;
 }
 
+// the decoder-likelihood epilogues: Gaussian (two channels: mean, logsigma) and Bernoulli (one channel: the logit)
+__host__ __device__ inline bool gauss_epi(int e) { return e == GPI_EPI_GAUSS_LOSS || e == GPI_EPI_GAUSS_EXP_LOSS; }
+__host__ __device__ inline bool loss_epi(int e) { return gauss_epi(e) || e == GPI_EPI_BERNOULLI_LOSS; }
+
 // NPX value of the forward's row-pair form (ConvGeom::npx, ShapeC::npxk): two vertically adjacent output
 // pixels x half of the output channels per thread
 constexpr int NPX_ROWS2 = -2;
@@ -214,7 +219,7 @@ __host__ __device__ constexpr int fwd_wci(int kk, int cp, int npx) {
 // measured 20.5 -> 29.7 us with it (profiles/r07_ab_fwd_rows2.txt)
 bool fwd_rows2(const gpi_conv_desc& d, const ConvGeom& G) {
     return d.k == 3 && d.stride == 1 && d.cout >= 3 && d.cout <= 8 && G.th * d.w_out == 256 &&
-           (d.w_out == 16 || d.w_out == 32) && d.epilogue != GPI_EPI_GAUSS_LOSS && d.epilogue != GPI_EPI_GAUSS_EXP_LOSS;
+           (d.w_out == 16 || d.w_out == 32) && !loss_epi(d.epilogue);
 }
 
 // The per-tile quantities of tiles of th output rows on row images of pitch P (input) and PG (output gradient)
@@ -293,7 +298,7 @@ bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fw
     // the backward of the loss-epilogue output conv (fused with its forward, K - 1 extra forward rows
     // per tile): 1024 px (r02 A/B: 16 rows 9 us per step faster than 8).  Keyed on the op, not on the
     // fusion, so gpi_conv_blocks' slab rows fit both launch forms.
-    const bool loss_bwd = !fwd && (d.epilogue == GPI_EPI_GAUSS_LOSS || d.epilogue == GPI_EPI_GAUSS_EXP_LOSS);
+    const bool loss_bwd = !fwd && loss_epi(d.epilogue);
     G.th = (loss_bwd ? t_fuse : target) / d.w_out;
     if (G.th < 1) G.th = 1;
     if (G.th > d.h_out) G.th = d.h_out;
@@ -337,7 +342,7 @@ bool conv_geom(const gpi_conv_desc& d, const gpi_groups& g, ConvGeom& G, bool fw
         while (2 * G.npx <= npx_cap && tp >= 256 * 2 * G.npx && d.w_out % (2 * G.npx) == 0) G.npx *= 2;
     }
     G.cg = 1;
-    if (fwd && G.npx == 1 && d.epilogue != GPI_EPI_GAUSS_LOSS && d.epilogue != GPI_EPI_GAUSS_EXP_LOSS) {
+    if (fwd && G.npx == 1 && !loss_epi(d.epilogue)) {
         // (kept on: without channel groups the C64 step is 1.9 us faster in the graph -- 0.5544 / 0.5552 / 0.5547
         // vs 0.5561 / 0.5567 / 0.5571 ms interleaved, profiles/r04z_ab_fwd_cg.txt -- but the one-chain channel
         // sum moves the 256^2 codec forward to 1.08e-5 of the fp64 oracle, over the 1e-5 bar, against 6.5e-6
@@ -873,6 +878,38 @@ __device__ __forceinline__ void store_px(float* p, const float (&v)[NPX]) {
     }
 }
 
+// Bernoulli log-likelihood of one pixel in the logit form (GPI_EPI_BERNOULLI_LOSS): logit a, target bit t (the
+// target value != the group's low-phase value tgt_lo).  ll = -softplus(-a) if t else -softplus(a) with
+// softplus(v) = max(v, 0) + log1p(exp(-|v|)): finite and unclamped for every a (no sigmoid that rounds to 1, no
+// clamped log); g = scl (sigmoid(a) - t), the sigmoid from the same e = exp(-|a|) <= 1.
+// Both transcendentals are written out for their ranges (x <= 0, e in (0, 1]) -- the library expf / log1pf carry
+// range selects and, log1pf, a double-float evaluation of ~20 live temporaries that spilled the fused kernel at
+// its 5-wave register budget:
+//   e = 2^(x log2 e), the product's rounding error and log2 e's own carried to first order (relative error
+//       1.2e-7 over |a| <= 30 plus the hardware exp2's ulp);
+//   log1p(e) = 2 atanh(s), s = e / (2 + e) <= 1/3, the odd series to s^13 (next term < 1.5e-8 relative; 3e-7
+//       relative overall down to e -> 0, where it tends to e itself).
+__device__ __forceinline__ void bern_px(float a, bool t, float scl, float& ll, float& g) {
+    const float x = -fabsf(a);
+    const float hi = x * 1.44269502f;                                        // fl(log2 e)
+    const float lo = fmaf(x, 1.92596299e-8f, fmaf(x, 1.44269502f, -hi));     // + x (log2 e - fl(log2 e))
+    const float p2 = __builtin_amdgcn_exp2f(hi);
+    const float e = fmaf(p2, lo * 0.693147182f, p2);
+    const float s = e * __builtin_amdgcn_rcpf(2.f + e), s2 = s * s;
+    float q = 1.f / 13.f;
+    q = fmaf(q, s2, 1.f / 11.f);
+    q = fmaf(q, s2, 1.f / 9.f);
+    q = fmaf(q, s2, 1.f / 7.f);
+    q = fmaf(q, s2, 1.f / 5.f);
+    q = fmaf(q, s2, 1.f / 3.f);
+    q = fmaf(q, s2, 1.f);
+    const float v = t ? -a : a;
+    ll = -(fmaxf(v, 0.f) + 2.f * s * q);
+    const float r = __builtin_amdgcn_rcpf(1.f + e);
+    const float sig = a >= 0.f ? r : e * r;
+    g = scl * (sig - (t ? 1.f : 0.f));
+}
+
 // ---------------------------------------------------------------------------------- forward
 // header floats: gst fp64 [4*MAX_CIN] | sc | sh [MAX_CIN] | scratch [64] | red [16] | dropout scales [8]
 constexpr int FWD_HDR = 8 * GPI_MAX_CIN + 2 * GPI_MAX_CIN + 64 + 16 + 8;
@@ -980,7 +1017,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
     float vst[2 * CP];
 #pragma unroll
     for (int q = 0; q < 2 * CP; ++q) vst[q] = 0.f;
-    const bool gauss = d.epilogue == GPI_EPI_GAUSS_LOSS || d.epilogue == GPI_EPI_GAUSS_EXP_LOSS;
+    const bool gauss = gauss_epi(d.epilogue);
+    // the Bernoulli epilogue: the binary decoder's 5x5 / stride-1 output conv with one output channel (launch()
+    // checks), so only that kernel's two-channel-slot instantiations carry it
+    const bool bern = K == 5 && S == 1 && !UP && CP == 2 && d.epilogue == GPI_EPI_BERNOULLI_LOSS;
     if constexpr (NPX > 1) {
         constexpr int PADK = K / 2;   // launch() checks pad == k / 2
         // window column of tap kx of pixel p (x0 is a multiple of NPX, even, for the upsampling offsets)
@@ -1054,6 +1094,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
                 }
             }
             const int64_t pix0 = (int64_t)oy * d.w_out + x0;
+            if (bern) {
+                if (active) {
+                    int row = T.b - karg_sel(c.groups.start, T.grp);
+                    if (const int32_t* ti = karg_sel(c.tgt_idx, T.grp)) row = ti[row];
+                    const float* tg = karg_sel(c.tgt, T.grp) + (int64_t)row * HWo + pix0;
+                    const float scl = karg_sel(c.loss_scale, T.grp), lo = karg_sel(c.tgt_lo, T.grp);
+                    float g0[NPX], m0[NPX];
+#pragma unroll
+                    for (int p = 0; p < NPX; ++p) {
+                        float ll;
+                        m0[p] = acc[p][0];
+                        bern_px(m0[p], tg[p] != lo, scl, ll, g0[p]);
+                        Lv += ll;
+                    }
+                    store_px<NPX>(ws + d.gout_off + (int64_t)T.b * HWo + pix0, g0);      // one plane: [B][1][H][W]
+                    if (d.out_off >= 0)
+                        store_px<NPX>(ws + d.out_off + ((int64_t)T.b * d.out_ctot + d.out_c0) * HWo + pix0, m0);
+                }
+                continue;
+            }
             if (gauss) {
                 if (active) {
                     int row = T.b - karg_sel(c.groups.start, T.grp);
@@ -1275,7 +1335,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
             const int oy = T.oy0 + ty, ox = tx;
             bool active = pix < tp && grp < cg;
             float tgt = 0.f;
-            if (gauss && active) {
+            if ((gauss || bern) && active) {
                 int row = T.b - karg_sel(c.groups.start, T.grp);
                 if (const int32_t* ti = karg_sel(c.tgt_idx, T.grp)) row = ti[row];
                 tgt = karg_sel(c.tgt, T.grp)[(int64_t)row * HWo + oy * d.w_out + ox];
@@ -1327,6 +1387,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
                 for (int co = 0; co < CP; ++co)
                     if (co < d.cout) acc[co] *= dsl[co];
             }
+            if (bern) {
+                if (active) {
+                    float ll, gv;
+                    bern_px(acc[0], tgt != karg_sel(c.tgt_lo, T.grp), karg_sel(c.loss_scale, T.grp), ll, gv);
+                    Lv += ll;
+                    *as_gst(ws + d.gout_off + (int64_t)T.b * HWo + oy * d.w_out + ox) = gv;
+                    if (d.out_off >= 0)
+                        *as_gst(ws + d.out_off + (int64_t)T.b * d.out_ctot * HWo + (int64_t)d.out_c0 * HWo +
+                                oy * d.w_out + ox) = acc[0];
+                }
+                continue;
+            }
             if (gauss) {
                 if (active) {
                     const float mu = acc[0], ls = acc[1];
@@ -1366,7 +1438,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
         }
     }
 
-    if (!ROWS2 && (d.epilogue == GPI_EPI_GAUSS_LOSS || d.epilogue == GPI_EPI_GAUSS_EXP_LOSS)) {   // (fwd_rows2: never)
+    if (!ROWS2 && (gauss || bern)) {   // (fwd_rows2: never)
         float v[1] = {Lv};
         block_sum<1>(v, scratch, red);      // thread 0 wrote red[0] itself: no barrier before reading it
         if (tid == 0 && !SKIP(G, 4)) atomicAdd(c.loss_acc + T.grp * GPI_REPLICAS + blockIdx.x % GPI_REPLICAS, (double)red[0]);
@@ -1446,7 +1518,17 @@ constexpr int GPI_FUSE_WAVES = 5;
 // generic kernel spills 14-15)
 constexpr int GPI_FUSE_SHP_WAVES = 5;
 
-template <int K, int S, int UP, bool FUSE = false, bool HALF = false, bool EXF = false, int SHP = -1>
+// broadcast of a forward input value over the fused loss phase's accumulator: the (co 0, co 1) pair of the Gaussian
+// forms, one float of the one-channel Bernoulli form
+template <typename T>
+__device__ __forceinline__ T splat(float v);
+template <>
+__device__ __forceinline__ float splat<float>(float v) { return v; }
+template <>
+__device__ __forceinline__ f32x2 splat<f32x2>(float v) { return f32x2{v, v}; }
+
+// EXF: the fused launch's loss form -- 0 Gaussian, 1 Gaussian of the exponentiated field, 2 Bernoulli (cout = 1)
+template <int K, int S, int UP, bool FUSE = false, bool HALF = false, int EXF = 0, int SHP = -1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (FUSE ? (SHP >= 0 ? GPI_FUSE_SHP_WAVES : GPI_FUSE_WAVES) : 4) : GPI_BWD_WAVES))) void conv_bwd_kernel(gpi_conv_desc d, gpi_codec_ctx c, ConvGeom G) {
     fold_shape<SHP>(d, G);
     touch_kernargs<CONV_KARG_BYTES>();
@@ -1541,16 +1623,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
         for (int e = tid; e < gimg / 4; e += 256) g4[e] = float4{0.f, 0.f, 0.f, 0.f};
     }
     const int CIV = d.cin <= 2 ? 2 : 4;      // vop: input channels per weight vector (zero padded)
+    constexpr int NCO = EXF == 2 ? 1 : 2;    // FUSE: output channels of the forward recompute (launch() checks cout)
     if (vop) {
         // weights W[co][ci][ky][kx] transposed for the packed (v_pk_fma_f32) loops: input gradient
-        // WB[((co K + ky) K + kx) CIV + ci]; FUSE forward WF[((ci K + kx) K + ky) 2 + co]
+        // WB[((co K + ky) K + kx) CIV + ci]; FUSE forward WF[((ci K + kx) K + ky) NCO + co]
         stage(mid, d.cout * KK * CIV, params + w_off, d.cout * d.cin * KK, [&](int e) -> int {
             const int ci = e % CIV, t = e / CIV, co = t / KK, tap = t - co * KK;
             return ci < d.cin ? (co * d.cin + ci) * KK + tap : -1;
         });
         if (FUSE)
-            stage(mid + 256, d.cin * KK * 2, params + w_off, d.cout * d.cin * KK, [&](int e) -> int {
-                const int co = e & 1, t = e >> 1, ci = t / KK, r = t - ci * KK, kx = r / K, ky = r - kx * K;
+            stage(mid + 256, d.cin * KK * NCO, params + w_off, d.cout * d.cin * KK, [&](int e) -> int {
+                const int co = NCO == 2 ? e & 1 : 0, t = NCO == 2 ? e >> 1 : e;
+                const int ci = t / KK, r = t - ci * KK, kx = r / K, ky = r - kx * K;
                 return (co * d.cin + ci) * KK + ky * K + kx;
             });
     }
@@ -1660,6 +1744,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
     __syncthreads();
     if (SKIP(G, 8)) return;
     PHASE(2);
+    // Bernoulli form: a target is one bit -- the first forward item's RPF targets (landed by now) packed into ONE
+    // register for the way through the forward loop (the loop runs at the kernel's register budget).  (A constant
+    // 0 in every other instantiation: it folds away.)
+    uint32_t tb0 = 0;
+    if constexpr (FUSE && EXF == 2) {
+        const float lo = karg_sel(c.tgt_lo, T.grp);
+#pragma unroll
+        for (int p = 0; p < RPF; ++p) tb0 |= (tv0[p] != lo ? 1u : 0u) << p;
+    }
 
     // ---- phase 2: coefficients
     if (tid < d.cin && d.in_bn) {
@@ -1811,8 +1904,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
         float Lv = 0.f;
         // the exp-field loss is an instantiation of its own (EXF; launch() picks it from d.epilogue): as a
         // runtime flag its two extra exps per pixel ran as selects in the log-field form as well
-        constexpr bool ex = EXF;
+        constexpr bool ex = EXF == 1;
+        // the Bernoulli form (EXF == 2): ONE channel, the logit -- a float accumulator and one FMA per tap, the
+        // tap's weight by a broadcast ds_read_b32, and one plane of the gradient image
+        constexpr bool bern = EXF == 2;
+        using acc_t = std::conditional_t<bern, float, f32x2>;
         const float scl = karg_sel(c.loss_scale, T.grp);
+        const float xlo = bern ? karg_sel(c.tgt_lo, T.grp) : 0.f;
         // RPF vertically adjacent pixels of one column per thread: items (column, row group) fill the
         // 256 lanes exactly on 64-wide planes (20 rows = 4 groups x 64 columns with 16-row tiles).  Per
         // (ci, kx) the column's RPF + K - 1 input values are read once (lanes on consecutive columns: one
@@ -1825,30 +1923,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
             for (int it = tid; it < nitem; it += 256) {
                 const int rg = dq(it, Gt.d_wout), x = it - rg * d.w_out;
                 const int j0 = rg * RPF;
-                float tv[RPF];
+                float tv[bern ? 1 : RPF];     // Gaussian forms: the item's targets
+                uint32_t tb = tb0;            // Bernoulli form: the item's target bits
+                if constexpr (bern) {
+                    if (it != tid) {          // (planes wider than 64: a later item's targets, packed as they land)
+                        tb = 0;
 #pragma unroll
-                for (int p = 0; p < RPF; ++p) {
-                    const int oy = gy0 + j0 + p;
-                    const bool ok = j0 + p < Gt.gh && oy >= 0 && oy < d.h_out;
-                    tv[p] = it == tid ? tv0[p] : (ok ? as_gld(tg)[oy * d.w_out + x] : 0.f);
+                        for (int p = 0; p < RPF; ++p) {
+                            const int oy = gy0 + j0 + p;
+                            const bool ok = j0 + p < Gt.gh && oy >= 0 && oy < d.h_out;
+                            tb |= ((ok ? as_gld(tg)[oy * d.w_out + x] : 0.f) != xlo ? 1u : 0u) << p;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int p = 0; p < RPF; ++p) {
+                        const int oy = gy0 + j0 + p;
+                        const bool ok = j0 + p < Gt.gh && oy >= 0 && oy < d.h_out;
+                        tv[p] = it == tid ? tv0[p] : (ok ? as_gld(tg)[oy * d.w_out + x] : 0.f);
+                    }
                 }
-                f32x2 acc[RPF];
+                acc_t acc[RPF];
 #pragma unroll
-                for (int p = 0; p < RPF; ++p) acc[p] = f32x2{0.f, 0.f};
-#pragma unroll
+                for (int p = 0; p < RPF; ++p) acc[p] = splat<acc_t>(0.f);
+                // (Bernoulli form: one input channel per iteration -- unrolled over the channels the scheduler hoisted
+                // the LDS reads of several of them and spilled at the 5-wave budget)
+#pragma unroll(bern ? 1 : CIN)
                 for (int ci = 0; ci < CIN; ++ci) {
                     if (ci >= d.cin) break;
                     const float* acol = al + ci * Gt.rh * Gt.P + HALO + x - PADK;
-#pragma unroll
+#pragma unroll(bern ? 1 : K)
                     for (int kx = 0; kx < K; ++kx) {
                         float v[RPF + K - 1];
 #pragma unroll
                         for (int r = 0; r < RPF + K - 1; ++r) v[r] = acol[min(j0 + r, Gt.rh - 1) * Gt.P + kx];
-                        f32x2 w[K];
+                        acc_t w[K];
 #pragma unroll
                         for (int ky = 0; ky < K; ++ky) {
-                            const int i = ((ci * K + kx) * K + ky) * 2;
-                            w[ky] = *reinterpret_cast<const f32x2*>(mid + 256 + i);
+                            const int i = ((ci * K + kx) * K + ky) * NCO;
+                            w[ky] = *reinterpret_cast<const acc_t*>(mid + 256 + i);
                         }
                         // input row j0 + r feeds pixel p through tap ky = r - p
 #pragma unroll
@@ -1857,7 +1970,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                             for (int p = 0; p < RPF; ++p) {
                                 const int ky = r - p;
                                 if (ky < 0 || ky >= K) continue;
-                                acc[p] = __builtin_elementwise_fma(w[ky], f32x2{v[r], v[r]}, acc[p]);
+                                acc[p] = __builtin_elementwise_fma(w[ky], splat<acc_t>(v[r]), acc[p]);
                             }
                         }
                     }
@@ -1867,14 +1980,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                     const int j = j0 + p, oy = gy0 + j;
                     if (j >= Gt.gh || oy < 0 || oy >= d.h_out) continue;
                     const bool own = j >= PADK && j < PADK + Gt.th;
-                    const float mu = acc[p][0], ls = acc[p][1];
-                    const float e = expf(-2.f * ls);
-                    const float emu = ex ? expf(mu) : 1.f;
-                    const float r = ex ? expf(tv[p]) - emu : tv[p] - mu;
-                    if (own) Lv += -0.5f * (2.f * ls + r * r * e + GPI_LOG2PI);
                     float* g0 = gl + j * Gt.PG + HALO + x;
-                    g0[0] = -scl * r * e * emu;
-                    g0[gplane] = scl * (1.f - r * r * e);
+                    if constexpr (bern) {
+                        float ll, gv;
+                        bern_px(acc[p], ((tb >> p) & 1u) != 0, scl, ll, gv);
+                        if (own) Lv += ll;
+                        g0[0] = gv;
+                    } else {
+                        const float mu = acc[p][0], ls = acc[p][1];
+                        const float e = expf(-2.f * ls);
+                        const float emu = ex ? expf(mu) : 1.f;
+                        const float r = ex ? expf(tv[p]) - emu : tv[p] - mu;
+                        if (own) Lv += -0.5f * (2.f * ls + r * r * e + GPI_LOG2PI);
+                        g0[0] = -scl * r * e * emu;
+                        g0[gplane] = scl * (1.f - r * r * e);
+                    }
                 }
             }
         };
@@ -2550,7 +2670,7 @@ conv_kernel_t shape_kernel() {
     constexpr ShapeC s = kShapes[I];
     if constexpr (no_fold(I)) return nullptr;
     else if constexpr (s.fwd != 0) return conv_fwd_kernel<s.D_k, s.D_stride, s.D_upsample, s.cp, s.npxk, s.half != 0, I>;
-    else return conv_bwd_kernel<s.D_k, s.D_stride, s.upk, s.fusek != 0, s.half != 0, s.exf != 0, I>;
+    else return conv_bwd_kernel<s.D_k, s.D_stride, s.upk, s.fusek != 0, s.half != 0, s.exf, I>;
 }
 
 // kernel of entry LO + i, entries [LO, LO + n) instantiated here
@@ -2621,12 +2741,14 @@ conv_kernel_t pick(int cp, bool fwd, int npx, bool half, bool ucls = false) {
     return pick_cp<K, S, UP, 1>(cp, half);
 }
 
-// fuse: the fused output conv's launch (launch() checks its shape: 5x5 / stride 1), exf its exp-field loss form
+// fuse: the fused output conv's launch (launch() checks its shape: 5x5 / stride 1), exf its loss form (0 Gaussian,
+// 1 exponentiated-field Gaussian, 2 Bernoulli)
 conv_kernel_t select_kernel(const gpi_conv_desc& d, int cp, bool fwd, int npx, bool half, bool ucls, bool fuse,
-                            bool exf) {
+                            int exf) {
     if (fuse) {
-        if (half) return exf ? conv_bwd_kernel<5, 1, 0, true, true, true> : conv_bwd_kernel<5, 1, 0, true, true>;
-        return exf ? conv_bwd_kernel<5, 1, 0, true, false, true> : conv_bwd_kernel<5, 1, 0, true>;
+        if (exf == 2) return half ? conv_bwd_kernel<5, 1, 0, true, true, 2> : conv_bwd_kernel<5, 1, 0, true, false, 2>;
+        if (half) return exf ? conv_bwd_kernel<5, 1, 0, true, true, 1> : conv_bwd_kernel<5, 1, 0, true, true>;
+        return exf ? conv_bwd_kernel<5, 1, 0, true, false, 1> : conv_bwd_kernel<5, 1, 0, true>;
     }
     const int key = d.k * 100 + d.stride * 10 + d.upsample;
     switch (key) {
@@ -2681,7 +2803,7 @@ bool xcd_mode(bool fwd, bool fuse, bool split, bool half) {
 // The shape of a planned launch (compile-time shapes above): the kernel variant select_kernel picks, the
 // B-independent descriptor fields and the geometry.  Unused bytes stay zero (value-initialised), so two
 // shapes compare by their bytes.
-ShapeC shape_of(const gpi_conv_desc& d, const ConvGeom& G, bool fwd, bool fuse, int cp, bool exf) {
+ShapeC shape_of(const gpi_conv_desc& d, const ConvGeom& G, bool fwd, bool fuse, int cp, int exf) {
     ShapeC s{};
     const bool half = G.nfull < G.nblocks;
     s.fwd = fwd;
@@ -2754,17 +2876,24 @@ int launch(const gpi_conv_desc& d, const gpi_codec_ctx& c, hipStream_t st, bool 
     if (sig && !sig_epoch) return GPI_ERR_ARG;
     G.sig = sig;
     G.sig_epoch = sig_epoch;
-    if (fuse && (fwd || d.k != 5 || d.stride != 1 || d.upsample || d.cout != 2 || d.cin > 4 || d.drop_off >= 0 ||
-                 d.gout_mode != 1 || d.gin_off < 0 ||
-                 (d.epilogue != GPI_EPI_GAUSS_LOSS && d.epilogue != GPI_EPI_GAUSS_EXP_LOSS)))
+    const bool bern = d.epilogue == GPI_EPI_BERNOULLI_LOSS;
+    // the Bernoulli epilogue: one logit channel, a direct output gradient, and (where the loss is computed: the
+    // forward and the fused launch) a target per group
+    if (bern && (d.cout != 1 || d.gout_mode != 1)) return GPI_ERR_ARG;
+    if (bern && (d.k != 5 || d.stride != 1 || d.upsample)) return GPI_ERR_UNSUPPORTED;   // the decoder's output conv only
+    if (bern && (fwd || fuse) && !dry)
+        for (int g = 0; g < c.groups.n_groups; ++g)
+            if (!c.tgt[g]) return GPI_ERR_ARG;
+    if (fuse && (fwd || d.k != 5 || d.stride != 1 || d.upsample || d.cout != (bern ? 1 : 2) || d.cin > 4 ||
+                 d.drop_off >= 0 || d.gout_mode != 1 || d.gin_off < 0 || !loss_epi(d.epilogue)))
         return GPI_ERR_UNSUPPORTED;
-    if ((d.epilogue == GPI_EPI_GAUSS_LOSS || d.epilogue == GPI_EPI_GAUSS_EXP_LOSS) && d.cout != 2) return GPI_ERR_ARG;
+    if (gauss_epi(d.epilogue) && d.cout != 2) return GPI_ERR_ARG;
     if (d.in_off < 0 && !c.ext_in) return GPI_ERR_ARG;
     if (!aligned_ok(d, c, fwd)) return GPI_ERR_UNSUPPORTED;
     if (!fwd && d.gin_off >= 0 && ((G.ph * d.w_in) & 15)) return GPI_ERR_UNSUPPORTED;
     if (!fwd && d.gin_off >= 0 && d.stride == 2 && ((d.w_in & 7) || (G.ph & 1))) return GPI_ERR_UNSUPPORTED;
     const int cp = cp_of(d);
-    const bool exf = d.epilogue == GPI_EPI_GAUSS_EXP_LOSS;
+    const int exf = bern ? 2 : d.epilogue == GPI_EPI_GAUSS_EXP_LOSS ? 1 : 0;
     conv_kernel_t k = select_kernel(d, cp, fwd, G.cg > 1 ? 0 : G.npx, G.nfull < G.nblocks, G.ucls != 0, fuse, exf);
     if (!k) return GPI_ERR_UNSUPPORTED;
     static const float* zero = nullptr;

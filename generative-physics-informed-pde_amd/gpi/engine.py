@@ -246,10 +246,14 @@ class ElboEngine(object):
             d_feat = 1
         # ---- decoder program (groups: unsup, sup, vo)
         dc = dec.native_config()
-        # the decoder likelihood of generative.py:232-239: log-property Gaussian (default) or the
-        # exponentiated field's (reconstruct_log_eff_property = False)
+        # the decoder likelihood of generative.py:232-244: log-property Gaussian (default) or the
+        # exponentiated field's (reconstruct_log_eff_property = False); a binary decoder (one logit channel)
+        # takes the Bernoulli likelihood whatever that option says -- the reference tests the prediction's
+        # type first
         log_field = getattr(model, 'config', {}).get('reconstruct_log_eff_property', True)
-        self.dp = decoder_program(final_epilogue=L.EPI_GAUSS_LOSS if log_field else L.EPI_GAUSS_EXP_LOSS, **dc)
+        self.binary = bool(getattr(dec, '_binary', False))
+        epi = L.EPI_BERNOULLI_LOSS if self.binary else (L.EPI_GAUSS_LOSS if log_field else L.EPI_GAUSS_EXP_LOSS)
+        self.dp = decoder_program(final_epilogue=epi, **dc)
         self.dec_sizes = [n for n in (self.B_u, self.N_s, self.N_vo) if n > 0]
         self.g_sup = (1 if self.B_u > 0 else 0) if self.N_s > 0 else None
         self.g_vo = ((self.B_u > 0) + (self.N_s > 0)) if self.N_vo > 0 else None
@@ -537,8 +541,17 @@ class ElboEngine(object):
         """Point the launch descriptors at this step's data tensors.  The engine keeps them alive
         until the next bind: the backward reads X_u again (the input conv's weight gradient), so a
         caller's temporary (e.g. a random-subset gather) must not return to the allocator between
-        the forward and the backward."""
+        the forward and the backward.
+        Binary decoder: each bound group's low-phase value tgt_lo = the minimum of the tensor bound to it
+        (the reference's target == target.min() rule, generative.py:241-242; for X_u with u_index that is
+        the pool's minimum) -- one torch reduction and host read (a device synchronisation) per bound tensor,
+        outside any captured step, and only when the tensor is new: the minimum is kept per (storage, version,
+        shape), so the module path's repeated elbo() calls on the same dataset tensors do not synchronise again."""
         self._bound = (X_u, u_index, X_s, Y, F, X_vo, F_vo)
+        if self.binary:
+            for gi, t in ((0 if self.B_u > 0 else None, X_u), (self.g_sup, X_s), (self.g_vo, X_vo)):
+                if gi is not None:
+                    self.dctx.tgt_lo[gi] = self._target_low(t)
         if self.B_u > 0:
             L.require_device(X_u)
             assert X_u.dtype == torch.float32 and X_u.is_contiguous()
@@ -568,6 +581,18 @@ class ElboEngine(object):
             if not self.vo_holdoff:
                 assert F_vo.shape[0] == self.N_vo
                 self.rom_vo.F = F_vo.data_ptr()
+
+    def _target_low(self, t):
+        """min(t) of a bound target tensor, read to the host once per (storage, in-place version, shape).  An
+        entry keeps its tensor alive, so the allocator cannot hand its address to other data while the entry
+        stands; a random-subset gather is a new tensor every call and takes the reduction every time."""
+        key = (t.data_ptr(), t._version, tuple(t.shape))
+        cache = self.__dict__.setdefault('_tgt_lo_cache', {})
+        if key not in cache:
+            if len(cache) >= 8:
+                cache.clear()
+            cache[key] = (t, float(t.min().item()))
+        return cache[key][1]
 
     def forward(self, stream=None, compute_value=True, zero_gacc=True, zero_scratch=True, running='now'):
         """Launch the forward; returns the 0-d ELBO tensor (no host sync).  zero_gacc / zero_scratch

@@ -149,11 +149,13 @@ class EvalEncoderEngine(object):
 
 
 class EvalDecoderEngine(object):
-    """CNNDecoder.forward in eval mode: z -> (mean, logsigma) [B, 2, H, W], forward only."""
+    """CNNDecoder.forward in eval mode: z -> (mean, logsigma) [B, 2, H, W], or the probability image
+    [B, 1, H, W] of a binary decoder (the sigmoid of the kernels' logit image); forward only."""
     mode = 'eval'
 
     def __init__(self, dec, flat, B):
         self.flat, self.B = flat, int(B)
+        self.binary = bool(getattr(dec, '_binary', False))
         dev = flat.P.device
         ws = Workspace()
         self.ws = ws
@@ -187,7 +189,8 @@ class EvalDecoderEngine(object):
              C.c_void_p(self.ws.t_ws.data_ptr()), st, what='latent map')
         self.seed.launch(st)
         _run(lib.gpi_codec_forward, self.descs, len(self.descs), C.byref(self.ctx), st, what='decoder eval forward')
-        return self.ws.view(self.p.output.off, *self.out_shape).clone()
+        out = self.ws.view(self.p.output.off, *self.out_shape)
+        return torch.sigmoid(out) if self.binary else out.clone()
 
 
 # ---------------------------------------------------------------- surrogate predictor

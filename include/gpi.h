@@ -58,6 +58,10 @@ extern "C" {
 #define GPI_EPI_GAUSS_LOSS 2   /* cout == 2: (mean, logsigma) -> Gaussian log-lik vs target, writes d(-elbo)/d(out) */
 #define GPI_EPI_GAUSS_EXP_LOSS 3  /* as GAUSS_LOSS on the exponentiated field: N(exp(target); exp(mean), sigma^2)
                                      (generative.py:238-239, reconstruct_log_eff_property = False) */
+#define GPI_EPI_BERNOULLI_LOSS 4  /* cout == 1: logit a -> Bernoulli log-lik of the target bit t = (target != tgt_lo[group])
+                                     in the logit form (-softplus(-a) if t else -softplus(a)), writes
+                                     d(-elbo)/d(a) = loss_scale (sigmoid(a) - t); the binary CNNDecoder
+                                     (Decoder.py:204-207, generative.py:232-244) */
 
 /* Per-channel BatchNorm statistics record, one per (channel, group). */
 typedef struct gpi_stat {
@@ -120,10 +124,12 @@ typedef struct gpi_codec_ctx {
     const float* ext_in;           /* external input (e.g. the unlabeled image pool) */
     const int32_t* ext_idx;        /* row of ext_in for each sample (NULL: identity) */
     int64_t ext_stride;            /* floats per ext_in row */
-    const float* tgt[GPI_MAX_GROUPS];      /* Gaussian-loss targets per group */
+    const float* tgt[GPI_MAX_GROUPS];      /* loss targets per group (Gaussian and Bernoulli epilogues) */
     const int32_t* tgt_idx[GPI_MAX_GROUPS];/* target row per sample of the group (NULL: identity) */
     float loss_scale[GPI_MAX_GROUPS];      /* d(-elbo)/d(logL): 1, or 1/batch when normalize */
-    double* loss_acc;              /* [GPI_MAX_GROUPS][GPI_REPLICAS] Gaussian log-likelihood sums */
+    float tgt_lo[GPI_MAX_GROUPS];          /* Bernoulli loss: the group's low-phase target value (its target tensor's
+                                              minimum); a pixel equal to it is bit 0, any other bit 1 */
+    double* loss_acc;              /* [GPI_MAX_GROUPS][GPI_REPLICAS] decoder log-likelihood sums */
     int64_t n_stats;               /* stat records per replica */
     float bn_eps;                  /* 1e-5 (torch default) */
     gpi_groups groups;
@@ -651,7 +657,9 @@ int gpi_conv_backward(const gpi_conv_desc* op, const gpi_codec_ctx* ctx, void* s
  * launch: adds the log-likelihood to ctx->loss_acc and writes the weight-gradient slab rows and the
  * input's S / BN-backward sums exactly as gpi_conv_forward followed by gpi_conv_backward would (the
  * output gradient never leaves LDS).  op: k = 5, stride 1, no upsampling, cin <= 4, cout = 2,
- * epilogue GPI_EPI_GAUSS_LOSS / GPI_EPI_GAUSS_EXP_LOSS, gout_mode 1, no dropout; out_off is ignored. */
+ * epilogue GPI_EPI_GAUSS_LOSS / GPI_EPI_GAUSS_EXP_LOSS, gout_mode 1, no dropout; out_off is ignored.
+ * With epilogue GPI_EPI_BERNOULLI_LOSS the op has cout = 1 (the binary decoder's logit) and the launch is the
+ * kernel's one-channel instantiation: one forward accumulator and one gradient plane per pixel. */
 int gpi_conv_loss_fused(const gpi_conv_desc* op, const gpi_codec_ctx* ctx, void* stream);
 /* Run a codec program: ops in order (forward) / reverse order (backward). */
 int gpi_codec_forward(const gpi_conv_desc* ops, int n_ops, const gpi_codec_ctx* ctx, void* stream);

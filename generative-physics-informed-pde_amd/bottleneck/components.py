@@ -6,8 +6,10 @@ import numpy as np
 import torch
 
 import lamp.modules
+from lamp.neuralnets import FeedforwardNeuralNetwork
 from bottleneck.ROM import ROM
 from bottleneck.utils import UnitGaussianKullbackLeiblerDivergence
+from gpi.engine import gp_linears
 from gpi.native import RomOperatorFunction
 
 
@@ -126,14 +128,18 @@ class VariationalApproximation(lamp.modules.BaseModule):
 
 
 class EffectivePropertyMap(lamp.modules.BaseModule):
-    """z -> log effective properties (components.py:201-256); 0 hidden layers."""
+    """z -> log effective properties (components.py:201-256): one nn.Linear, or with num_hidden_layers = L > 0
+    the reference's ReLU MLP of linearly decaying widths (lamp/neuralnets.py; native form csrc/gpmlp.hip)."""
 
     def __init__(self, latent_dim, dim_effective_property, num_hidden_layers=0, independent_X=True, *, dtype=None,
                  device=None):
         super().__init__()
         if num_hidden_layers:
-            raise NotImplementedError('hidden layers in the effective-property map are not on the ELBO path')
-        self.fc = torch.nn.Linear(latent_dim, dim_effective_property)
+            self.fc = FeedforwardNeuralNetwork.FromLinearDecay(latent_dim, dim_effective_property,
+                                                               int(num_hidden_layers), outf=None, dropout=None,
+                                                               dtype=dtype, device=device)
+        else:
+            self.fc = torch.nn.Linear(latent_dim, dim_effective_property)
         if independent_X:
             self.logsigmas_X = torch.nn.Parameter(torch.ones(dim_effective_property))
         self._latent_dim = latent_dim
@@ -147,6 +153,10 @@ class EffectivePropertyMap(lamp.modules.BaseModule):
     @property
     def dim_in(self):
         return self._latent_dim
+
+    @property
+    def num_hidden_layers(self):
+        return len(gp_linears(self.fc)) - 1
 
     def forward(self, z):
         if self._independent_X:

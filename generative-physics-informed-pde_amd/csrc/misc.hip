@@ -523,7 +523,8 @@ extern "C" int gpi_struct_sizes(int64_t* out, int n) {
                          (int64_t)sizeof(gpi_fom_desc), (int64_t)sizeof(gpi_random_field_desc),
                          (int64_t)sizeof(gpi_vo_sparse), (int64_t)sizeof(gpi_draw_item),
                          (int64_t)sizeof(gpi_bn_exchange_desc), (int64_t)sizeof(gpi_bn_eval_item),
-                         (int64_t)sizeof(gpi_vo_energy_desc), (int64_t)sizeof(gpi_rom_fit_desc)};
+                         (int64_t)sizeof(gpi_vo_energy_desc), (int64_t)sizeof(gpi_rom_fit_desc),
+                         (int64_t)sizeof(gpi_gpmlp_desc), (int64_t)sizeof(gpi_gpmlp_sample_desc)};
     const int k = (int)(sizeof(s) / sizeof(s[0]));
     if (!out || n < k) return GPI_ERR_ARG;
     for (int i = 0; i < k; ++i) out[i] = s[i];

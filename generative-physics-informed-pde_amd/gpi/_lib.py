@@ -167,6 +167,26 @@ class GpSampleDesc(C.Structure):
                 ('seed', u64), ('offset', vp), ('sub', u64), ('x', vp)]
 
 
+GPMLP_MAX_HIDDEN = 3
+GPMLP_LOCKX = 0x1
+
+
+class GpMlpDesc(C.Structure):
+    _fields_ = [('n_layers', i32), ('n1', i32), ('n2', i32), ('flags', i32), ('width', i32 * (GPMLP_MAX_HIDDEN + 2)),
+                ('_pad', i32), ('w', i64 * (GPMLP_MAX_HIDDEN + 1)), ('b', i64 * (GPMLP_MAX_HIDDEN + 1)), ('gp_ls', i64),
+                ('qx_mu', i64), ('qx_ls', i64), ('qx_mu2', i64), ('qx_ls2', i64),
+                ('qz_mu', i64), ('qz_ls', i64), ('qz_mu2', i64), ('qz_ls2', i64), ('z', i64), ('eps_z', i64),
+                ('h', i64 * GPMLP_MAX_HIDDEN), ('dh', i64 * GPMLP_MAX_HIDDEN),
+                ('eps_x', i64), ('xs', i64), ('mux', i64), ('gxs', i64), ('gmux', i64), ('dz', i64),
+                ('lx_scale', f32), ('lx_scale2', f32), ('terms', vp), ('terms2', vp)]
+
+
+class GpMlpSampleDesc(C.Structure):
+    _fields_ = [('rows', i32), ('rep', i32), ('n_layers', i32), ('width', i32 * (GPMLP_MAX_HIDDEN + 2)),
+                ('qz_mu', vp), ('qz_ls', vp), ('w', vp * (GPMLP_MAX_HIDDEN + 1)), ('b', vp * (GPMLP_MAX_HIDDEN + 1)),
+                ('gp_ls', vp), ('eps_z', vp), ('eps_x', vp), ('seed', u64), ('offset', vp), ('sub', u64), ('x', vp)]
+
+
 class VoGalerkinDesc(C.Structure):
     _fields_ = [('n_fine', i32), ('n', i32), ('m_aux', i32), ('kind', i32),
                 ('logkappa', vp), ('bc', vp), ('V', vp), ('centers', vp), ('length', C.c_double),
@@ -231,7 +251,7 @@ class BnExchangeDesc(C.Structure):
 STRUCTS = [Stat, Groups, ConvDesc, CodecCtx, ReduceItem, HeadDesc, GemmItem, RomDesc, ResidualDesc, AdamDesc,
            VoQueryDesc, VoMomentsDesc, VoConditionDesc, VoPrecisionDesc, GpSampleDesc,
            VoGalerkinDesc, StepEpilogueDesc, FomDesc, RandomFieldDesc, VoSparse, DrawItem, BnExchangeDesc,
-           BnEvalItem, VoEnergyDesc, RomFitDesc]
+           BnEvalItem, VoEnergyDesc, RomFitDesc, GpMlpDesc, GpMlpSampleDesc]
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -301,6 +321,9 @@ SIGNATURES = {
     'gpi_gauss_sample': (C.c_int, [vp, vp, vp, i64, i32, i32, vp, u64, vp, u64, vp]),
     'gpi_gp_sample': (C.c_int, [C.POINTER(GpSampleDesc), vp]),
     'gpi_predictive_scores': (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
+    'gpi_gpmlp_forward': (C.c_int, [C.POINTER(GpMlpDesc), vp, vp, vp]),
+    'gpi_gpmlp_backward': (C.c_int, [C.POINTER(GpMlpDesc), vp, vp, vp, vp]),
+    'gpi_gpmlp_sample': (C.c_int, [C.POINTER(GpMlpSampleDesc), vp]),
 }
 
 _LIB = None

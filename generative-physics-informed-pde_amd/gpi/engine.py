@@ -18,6 +18,7 @@ unsupervised term (generative.py:546-585) + the supervised freeX term
 import ctypes as C
 import os
 import math
+import warnings
 
 import torch
 
@@ -89,6 +90,19 @@ class Workspace(object):
 
     def zero_scratch(self):
         self.t_scr.zero_()
+
+
+def gp_linears(gp):
+    """The nn.Linear layers of an effective-property map (EffectivePropertyMap, or a bare deterministic map):
+    the one Linear, or fc1 .. fc{L+1} of the MLP with L hidden layers (lamp/neuralnets.py)."""
+    fc = gp.fc if hasattr(gp, 'fc') else gp
+    return [fc] if isinstance(fc, torch.nn.Linear) else list(fc.linears)
+
+
+def check_gp_hidden(n_hidden):
+    if n_hidden > L.GPMLP_MAX_HIDDEN:
+        raise L.NativeError('the effective-property map has %d hidden layers; the native path supports at most %d '
+                            '(GPI_GPMLP_MAX_HIDDEN)' % (n_hidden, L.GPMLP_MAX_HIDDEN))
 
 
 def make_ctx(ws, flat, group_sizes):
@@ -275,6 +289,12 @@ class ElboEngine(object):
         d_x = g.dim_effective_property if self.N_q > 0 else 1
         self.d_x = d_x
         self.d_y = g.dim_out
+        # nonlinear effective-property map (L hidden layers): gpi_gpmlp_forward / _backward own the gp term of the
+        # q rows, the head runs without GPI_HEAD_GP.  L = 0: nothing of this exists -- no launch, no buffer.
+        gp_lin = gp_linears(gp) if self.N_x > 0 else []
+        self.gp_hidden = max(len(gp_lin) - 1, 0)
+        check_gp_hidden(self.gp_hidden)
+        self.gp_widths = ([gp_lin[0].in_features] + [fc.out_features for fc in gp_lin]) if self.gp_hidden else []
         hb = {}
         for name, n in (('hpre', self.B_u * d_feat), ('dhpre', self.B_u * d_feat),
                         ('zmu', self.B * dz), ('zls', self.B * dz), ('eps_z', self.B * dz), ('z', self.B * dz),
@@ -284,6 +304,12 @@ class ElboEngine(object):
                         ('y_vo', (self.N_vo if not self.vo_holdoff else 0) * self.d_y)):
             hb[name] = ws.alloc(max(n, 1))
         self.hb = hb
+        # h_k / delta_k [N_x, width_k] of the MLP's hidden layers
+        self.gp_mlp_buffers = {}
+        for k in range(1, self.gp_hidden + 1):
+            for name in ('h%d' % k, 'dh%d' % k):
+                self.gp_mlp_buffers[name] = ws.alloc(self.N_x * self.gp_widths[k])
+        self.gp_mlp_launches = 2 if self.gp_hidden else 0
         # ROM log-likelihood: per-sample d/dlogsigma_y rows (plain stores), reduced into gacc with the
         # decoder slabs (gpi_rom gls_part) -- instead of n x d_y same-address fp64 atomics
         self.gls_off = {}
@@ -296,7 +322,7 @@ class ElboEngine(object):
         h.flags = L.HEAD_LATENT
         if self.B_u > 0:
             h.flags |= (L.HEAD_ENC if self.armortized else 0) | L.HEAD_REPARAM
-        gpf = L.HEAD_GP | (L.HEAD_LOCKX if self.lockx else 0)
+        gpf = (L.HEAD_GP | (L.HEAD_LOCKX if self.lockx else 0)) if not self.gp_hidden else 0
         if self.N_s > 0:
             h.flags |= L.HEAD_QZ | gpf
         h.n_enc, h.n_q, h.n_q2 = self.B_u, self.N_s, self.N_vo
@@ -314,7 +340,7 @@ class ElboEngine(object):
         h.lat_w, h.lat_b = P(dec, 'latent_map.weight'), P(dec, 'latent_map.bias')
         h.gp_w = h.gp_b = h.gp_ls = h.qz_mu = h.qz_ls = h.qx_mu = h.qx_ls = -1
         h.qz_mu2 = h.qz_ls2 = h.qx_mu2 = h.qx_ls2 = -1
-        if self.N_x > 0:
+        if self.N_x > 0 and not self.gp_hidden:
             h.gp_w, h.gp_b = P(gp, 'fc.weight'), P(gp, 'fc.bias')
             if not self.lockx:
                 h.gp_ls = P(gp, 'logsigmas_X')
@@ -349,6 +375,30 @@ class ElboEngine(object):
         h.terms = ws.term_ptr(T_KL_ENC).value
         h.terms2 = ws.term_ptr(T_KL_Q2).value
         self.head = h
+        self.gpm = None
+        if self.gp_hidden:
+            m = L.GpMlpDesc()
+            m.n_layers, m.n1, m.n2 = self.gp_hidden, self.N_s, self.N_x - self.N_s
+            m.flags = L.GPMLP_LOCKX if self.lockx else 0
+            for k, w in enumerate(self.gp_widths):
+                m.width[k] = w
+            for k in range(L.GPMLP_MAX_HIDDEN + 1):
+                m.w[k] = flat.offset(gp_lin[k].weight) if k < len(gp_lin) else -1
+                m.b[k] = flat.offset(gp_lin[k].bias) if k < len(gp_lin) else -1
+            m.gp_ls = P(gp, 'logsigmas_X') if not self.lockx else -1
+            for k in ('qx_mu', 'qx_ls', 'qx_mu2', 'qx_ls2', 'qz_mu', 'qz_ls', 'qz_mu2', 'qz_ls2'):
+                setattr(m, k, getattr(h, k))
+            m.z, m.eps_z = hb['z'] + self.B_u * dz, hb['eps_z'] + self.B_u * dz
+            for k in range(L.GPMLP_MAX_HIDDEN):
+                m.h[k] = self.gp_mlp_buffers.get('h%d' % (k + 1), -1)
+                m.dh[k] = self.gp_mlp_buffers.get('dh%d' % (k + 1), -1)
+            for k in ('eps_x', 'xs', 'mux', 'gxs', 'gmux'):
+                setattr(m, k, hb[k])
+            m.dz = -1
+            m.lx_scale, m.lx_scale2 = ss, sv
+            m.terms = ws.term_ptr(T_LOGL_X).value
+            m.terms2 = ws.term_ptr(T_LOGL_X2).value
+            self.gpm = m
         # ---- contexts
         if self.ep is not None:
             self.ectx = make_ctx(ws, flat, [self.B_u])
@@ -375,8 +425,14 @@ class ElboEngine(object):
             gi.append(it)
 
         gemm(self.dp.input.s_off, hb['z'], B, d_lat, dz, d_lat, dz, h.lat_w, h.lat_b)
-        if self.N_x > 0:
+        if self.N_x > 0 and not self.gp_hidden:
             gemm(hb['gmux'], hb['z'] + self.B_u * dz, self.N_x, d_x, dz, d_x, dz, h.gp_w, h.gp_b)
+        for k in range(1, self.gp_hidden + 2) if self.gp_hidden else ():
+            # layer k of the MLP: sum over rows of delta_k (x) h_{k-1} (delta_{L+1} = gmux, h_0 = z)
+            wo, wi = self.gp_widths[k], self.gp_widths[k - 1]
+            a = hb['gmux'] if k == self.gp_hidden + 1 else self.gp_mlp_buffers['dh%d' % k]
+            b = hb['z'] + self.B_u * dz if k == 1 else self.gp_mlp_buffers['h%d' % (k - 1)]
+            gemm(a, b, self.N_x, wo, wi, wo, wi, self.gpm.w[k - 1], self.gpm.b[k - 1])
         if self.B_u > 0 and self.armortized:
             gemm(hb['dzmu'], hb['hpre'], self.B_u, dz, d_feat, dz, d_feat, h.mu_w, h.mu_b, 1)
             gemm(hb['dzls'], hb['hpre'], self.B_u, dz, d_feat, dz, d_feat, h.ls_w, h.ls_b, 1)
@@ -420,7 +476,11 @@ class ElboEngine(object):
         self.rom_reduce = []
         # GPI_ROM_EARLY=1 (free q_X only): the fused step's ROM runs at the very start of the step on
         # the side stream, its inputs drawn from q_X in the kernel, concurrently with the encoder
-        self.rom_draw = os.environ.get('GPI_ROM_EARLY', '0') == '1' and not self.lockx
+        # (not with the MLP map, whose forward runs ahead of the ROM on the side stream and needs the head's z)
+        self.rom_draw = os.environ.get('GPI_ROM_EARLY', '0') == '1' and not self.lockx and not self.gp_hidden
+        if os.environ.get('GPI_ROM_EARLY', '0') == '1' and self.gp_hidden and self.N_x > 0:
+            warnings.warn('GPI_ROM_EARLY=1 is ignored: the effective-property map has hidden layers, whose forward '
+                          'runs ahead of the ROM and needs the head forward (the default ROM order is used)')
         self.roms = []
         self.rom = self.rom_vo = None
         if self.N_s > 0:
@@ -510,6 +570,14 @@ class ElboEngine(object):
     def _head_backward(self, hd, st):
         _run(_lib().gpi_head_backward, C.byref(hd), C.c_void_p(self.flat.P.data_ptr()),
              C.c_void_p(self.ws.t_ws.data_ptr()), C.c_void_p(self.flat.gacc.data_ptr()), st, what='head backward')
+
+    def _gp_forward(self, st):
+        _run(_lib().gpi_gpmlp_forward, C.byref(self.gpm), C.c_void_p(self.flat.P.data_ptr()),
+             C.c_void_p(self.ws.t_ws.data_ptr()), st, what='gp mlp forward')
+
+    def _gp_backward(self, st):
+        _run(_lib().gpi_gpmlp_backward, C.byref(self.gpm), C.c_void_p(self.flat.P.data_ptr()),
+             C.c_void_p(self.ws.t_ws.data_ptr()), C.c_void_p(self.flat.gacc.data_ptr()), st, what='gp mlp backward')
 
     def eps_z(self):
         return self.ws.view(self.hb['eps_z'], self.B, self.dz)
@@ -680,9 +748,12 @@ class ElboEngine(object):
                  what='decoder output conv (forward + loss + backward)')
 
     def rom_side(self, sst):
-        """Side stream: the ROM solves (after the head forward)."""
+        """Side stream: the ROM solves (after the head forward); with the MLP effective-property map its
+        forward (mu_X, X~, logL_X, entropy from the head's z) ahead of them."""
         if self.side_pre is not None:
             self.side_pre(sst)
+        if self.gpm is not None:
+            self._gp_forward(sst)
         for r in self.roms:
             _run(_lib().gpi_rom, C.byref(r), sst, what='rom')
 
@@ -695,6 +766,8 @@ class ElboEngine(object):
             hd.flags |= L.HEAD_PART_ENC
             self._head_backward(hd, st)
         else:
+            if self.gpm is not None:
+                self._gp_backward(st)
             self._head_backward(self.head, st)
         if not self.armortized and self.B_u > 0:
             # d/dmu, d/dlogsigma of q_z['unsupervised'] (written by the head for its first segment)
@@ -736,6 +809,8 @@ class ElboEngine(object):
             self.rom_side(sst)
             self._rom_deferred = False
         if split:
+            if self.gpm is not None:
+                self._gp_backward(sst)          # needs the ROM adjoint, as the head's variational half
             hq = L.HeadDesc.from_buffer_copy(self.head)
             hq.flags |= L.HEAD_PART_Q
             self._head_backward(hq, sst)

@@ -21,7 +21,8 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import Workspace, groups_struct, make_ctx, rom_call, _run, _lib, T_KL_ENC, ROM_NN
+from .engine import (Workspace, groups_struct, make_ctx, rom_call, _run, _lib, T_KL_ENC, ROM_NN, gp_linears,
+                     check_gp_hidden)
 from .plan import encoder_program, decoder_program
 
 
@@ -230,8 +231,11 @@ class SurrogatePredictor(object):
         self.B = int(B)
         self.enc, self.gp, self.g = enc, gp, g
         self.fc = gp.fc if hasattr(gp, 'fc') else gp
-        dev = self.fc.weight.device
-        L.require_device(self.fc.weight)
+        # the map's nn.Linear layers: one (gpi_affine) or the MLP's fc1 .. fc{L+1} (gpi_gpmlp_sample, mean only)
+        self.linears = gp_linears(self.fc)
+        check_gp_hidden(len(self.linears) - 1)
+        dev = self.linears[0].weight.device
+        L.require_device(self.linears[0].weight)
         self.device = dev
         flat = module_flat(enc, dev)
         self.flat = flat
@@ -239,9 +243,9 @@ class SurrogatePredictor(object):
         rom = g.rom
         self.nc, self.refine = rom.nc, rom.refine
         self.d_x, self.d_y, self.dz = g.dim_effective_property, g.dim_out, self.engine.dz
-        if tuple(self.fc.weight.shape) != (self.d_x, self.dz):
+        if (self.linears[0].in_features, self.linears[-1].out_features) != (self.dz, self.d_x):
             raise ValueError('gp map %s does not take the encoder mean [%d] to the ROM input [%d]'
-                             % (tuple(self.fc.weight.shape), self.dz, self.d_x))
+                             % ((self.linears[0].in_features, self.linears[-1].out_features), self.dz, self.d_x))
         inp = self.engine.p.input
         self.X = torch.zeros(self.B, 1, inp.H, inp.W, dtype=torch.float32, device=dev)
         self.F = torch.zeros(self.B, ROM_NN(self.nc), dtype=torch.float32, device=dev)
@@ -254,17 +258,23 @@ class SurrogatePredictor(object):
     def _launch(self):
         st = L.stream_handle()
         self.engine.launch(self.X, st)
-        w, b = self.fc.weight, self.fc.bias
-        _run(_lib().gpi_affine, L.ptr(w), L.ptr(b), L.ptr(self.engine.mu), L.ptr(self.x_eff), self.B, self.d_x,
-             self.dz, st, what='gp mean')
+        if len(self.linears) > 1:
+            from .predictive import gp_mlp_sample
+            # (the launch reads the parameters' own storage: _check_params -- run by predict() and, before it bakes
+            # the pointers, by capture() -- requires contiguous fp32 weights, for which detach().contiguous() is a
+            # view, so nothing the returned keep-alive tuple holds can go away while the modules live)
+            gp_mlp_sample(self.linears, self.engine.mu, None, None, self.x_eff, stream=st)
+        else:
+            w, b = self.fc.weight, self.fc.bias
+            _run(_lib().gpi_affine, L.ptr(w), L.ptr(b), L.ptr(self.engine.mu), L.ptr(self.x_eff), self.B, self.d_x,
+                 self.dz, st, what='gp mean')
         rom_call(self.nc, self.refine, self.x_eff, self.F, False, L.ROM_FORWARD, mu_y=self.y, flag=self.flag)
 
     def _check_params(self):
         if not all(self.flat.owns(p) for p in self.enc.parameters()):
             raise L.NativeError('the encoder parameters were re-allocated since this SurrogatePredictor was built '
                                 '(module.to() / a new flat buffer): build a new predictor')
-        w, b = self.fc.weight, self.fc.bias
-        for t in (w,) + ((b,) if b is not None else ()):
+        for t in [p for fc in self.linears for p in (fc.weight, fc.bias) if p is not None]:
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
                 raise L.NativeError('gp map: contiguous fp32 parameters on %s expected' % self.device)
 

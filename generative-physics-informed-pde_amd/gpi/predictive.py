@@ -25,7 +25,7 @@ import torch
 
 from . import _lib as L
 from . import vo as V
-from .engine import ElboEngine, rom_call, ROM_NN
+from .engine import ElboEngine, rom_call, ROM_NN, gp_linears, check_gp_hidden
 from .flat import FlatParameters
 
 
@@ -35,6 +35,31 @@ def _p(t):
 
 def host_seed():
     return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def gp_mlp_sample(linears, q_mean, q_logsigma, gp_ls, x, rep=1, eps_z=None, eps_x=None, seed=0, sub=21,
+                  stream=None):
+    """x[r] = mlp(z_r) (+ exp(gp_ls) eps_x), z_r = q_mean[r // rep] (+ exp(q_logsigma[r // rep]) eps_z unless
+    q_logsigma is None) through gpi_gpmlp_sample, for the MLP's nn.Linear layers ``linears`` (fc1 .. fc{L+1});
+    noise injected (eps_z / eps_x) or Philox (seed, streams sub / sub + 1).  Returns the tensors the launch
+    reads (keep them alive until it has run)."""
+    check_gp_hidden(len(linears) - 1)
+    ws = [fc.weight.detach().contiguous() for fc in linears]
+    bs = [fc.bias.detach().contiguous() for fc in linears]
+    for t in ws + bs + [q_mean, x]:
+        L.require_device(t)
+        assert t.dtype == torch.float32
+    d = L.GpMlpSampleDesc(rows=x.shape[0], rep=int(rep), n_layers=len(linears) - 1, qz_mu=_p(q_mean),
+                          qz_ls=_p(q_logsigma), gp_ls=_p(gp_ls), eps_z=_p(eps_z), eps_x=_p(eps_x), seed=seed,
+                          offset=None, sub=sub, x=_p(x))
+    d.width[0] = linears[0].in_features
+    for k, fc in enumerate(linears):
+        d.width[k + 1] = fc.out_features
+        d.w[k], d.b[k] = _p(ws[k]), _p(bs[k])
+    assert d.width[0] == q_mean.shape[1] and d.width[len(linears)] == x.shape[1]
+    L.check(L.lib().gpi_gpmlp_sample(C.byref(d), stream if stream is not None else L.stream_handle()),
+            'gp mlp sample')
+    return ws, bs, q_mean, q_logsigma, gp_ls, eps_z, eps_x
 
 
 # ---------------------------------------------------------------- predictive y
@@ -51,15 +76,21 @@ def predictive_y(model, q_mean, q_logsigma, F, N_mc, eps=None, seed=None, return
     dev = q_mean.device
     seed = host_seed() if seed is None else seed
     x = torch.empty(rows, dx, dtype=torch.float32, device=dev)
-    w, b = gp.fc.weight.detach().contiguous(), gp.fc.bias.detach().contiguous()
-    assert w.shape == (dx, dz)
     ls = gp.logsigmas_X.detach().contiguous() if gp.independent_X else None
-    d = L.GpSampleDesc(rows=rows, rep=int(N_mc), d_z=dz, d_x=dx, qz_mu=_p(q_mean.detach().contiguous()),
-                       qz_ls=_p(q_logsigma.detach().contiguous()), gp_w=_p(w), gp_b=_p(b), gp_ls=_p(ls),
-                       eps_z=_p(eps[0]) if eps is not None else None, eps_x=_p(eps[1]) if eps is not None else None,
-                       seed=seed, offset=None, sub=21, x=_p(x))
-    keep = (q_mean, q_logsigma, w, b, ls)
-    L.check(L.lib().gpi_gp_sample(C.byref(d), L.stream_handle()), 'gp sample')
+    lin = gp_linears(gp)
+    qm, ql = q_mean.detach().contiguous(), q_logsigma.detach().contiguous()
+    if len(lin) > 1:
+        # MLP effective-property map: the same draws through gpi_gpmlp_sample
+        keep = gp_mlp_sample(lin, qm, ql, ls, x, rep=int(N_mc), eps_z=eps[0] if eps is not None else None,
+                             eps_x=eps[1] if eps is not None else None, seed=seed, sub=21)
+    else:
+        w, b = lin[0].weight.detach().contiguous(), lin[0].bias.detach().contiguous()
+        assert w.shape == (dx, dz)
+        d = L.GpSampleDesc(rows=rows, rep=int(N_mc), d_z=dz, d_x=dx, qz_mu=_p(qm), qz_ls=_p(ql), gp_w=_p(w),
+                           gp_b=_p(b), gp_ls=_p(ls), eps_z=_p(eps[0]) if eps is not None else None,
+                           eps_x=_p(eps[1]) if eps is not None else None, seed=seed, offset=None, sub=21, x=_p(x))
+        keep = (qm, ql, w, b, ls)
+        L.check(L.lib().gpi_gp_sample(C.byref(d), L.stream_handle()), 'gp sample')
     F_mc = F.float().repeat_interleave(int(N_mc), 0).contiguous()
     uc = torch.empty(rows, ROM_NN(rom.nc), dtype=torch.float32, device=dev)
     rom_call(rom.nc, rom.refine, x, F_mc, False, L.ROM_FORWARD, uc=uc)

@@ -892,6 +892,74 @@ typedef struct gpi_random_field_desc {
 } gpi_random_field_desc;
 int gpi_random_field(const gpi_random_field_desc* d, void* stream);
 
+/* ---- Nonlinear effective-property map: gp as a ReLU MLP with L hidden layers
+ * (lamp/neuralnets.py:7-44 FeedforwardNeuralNetwork / FromLinearDecay, bottleneck/components.py:207-210).
+ *   h_0 = z,  h_k = relu(W_k h_{k-1} + b_k) (k = 1..L),  mu_X = W_{L+1} h_L + b_{L+1}
+ * with widths width[0] = d_z, width[1..L] the hidden widths, width[L + 1] = d_x (each 1..512; any width, the
+ * kernels read weights element-wise, no row alignment is assumed) and torch Linear weights W_k [width[k]]
+ * [width[k - 1]].  1 <= L <= GPI_GPMLP_MAX_HIDDEN: L = 0 is the head's own gp product (GPI_ERR_ARG here), a
+ * larger L returns GPI_ERR_UNSUPPORTED.  Workgroups take tiles of 16 rows; every weight tile is read once per
+ * workgroup and staged through LDS, so a layer of any size within the width cap runs.
+ *
+ * gpi_gpmlp_forward / gpi_gpmlp_backward own the WHOLE gp term of the q rows [0, n1 + n2) that the head does
+ * with GPI_HEAD_GP for L = 0 (the head then runs with GPI_HEAD_GP cleared): the forward reads z (written by the
+ * head forward), stores h_k, mu_X and X~ and adds logL_X and the entropy to the term slots exactly as
+ * head.hip forms them per element (generative.py:464-478; GPI_GPMLP_LOCKX: X~ = mu_X, no terms); the backward
+ * forms delta_{L+1} = dJ/dmu_X (-lx_scale r e2 free-X, the ROM adjoint gxs lock-X) into gmux, the q_X rows' and
+ * logsigmas_X's gradients, delta_k = (W_{k+1}^T delta_{k+1}) * [h_k > 0] into dh_k, and adds W_1^T delta_1 to
+ * the q_z rows' gradients (d/dmean += v, d/dlogsigma += v exp(logsigma) eps_z: the head's own additions are
+ * linear in dJ/dz, the fp64 accumulator sums the two parts).  Weight / bias gradients are gpi_outer_gemm
+ * items over (dh_k | gmux, h_{k-1}).  Segment 1 = rows [0, n1), segment 2 = rows [n1, n1 + n2) with their own
+ * q rows, lx_scale and term slots. */
+#define GPI_GPMLP_MAX_HIDDEN 3
+#define GPI_GPMLP_LOCKX 0x1
+typedef struct gpi_gpmlp_desc {
+    int32_t n_layers;                          /* hidden layers L */
+    int32_t n1, n2;                            /* rows per segment */
+    int32_t flags;                             /* GPI_GPMLP_* */
+    int32_t width[GPI_GPMLP_MAX_HIDDEN + 2];
+    int32_t _pad;
+    /* parameter offsets (-1 if absent) */
+    int64_t w[GPI_GPMLP_MAX_HIDDEN + 1], b[GPI_GPMLP_MAX_HIDDEN + 1];
+    int64_t gp_ls;
+    int64_t qx_mu, qx_ls, qx_mu2, qx_ls2;
+    int64_t qz_mu, qz_ls, qz_mu2, qz_ls2;      /* backward only; -1: no q_z gradient for that segment */
+    /* workspace offsets of row 0 (all >= 0 when used: a negative offset of a buffer the launch touches is
+     * GPI_ERR_ARG; eps_z is read by the backward's q_z gradients only) */
+    int64_t z, eps_z;                          /* [n, d_z] */
+    int64_t h[GPI_GPMLP_MAX_HIDDEN];           /* h_k [n, width[k]] (post-ReLU) */
+    int64_t dh[GPI_GPMLP_MAX_HIDDEN];          /* delta_k [n, width[k]] */
+    int64_t eps_x, xs, mux, gxs, gmux;         /* [n, d_x] */
+    int64_t dz;                                /* optional (>= 0): W_1^T delta_1 [n, d_z] stored */
+    float lx_scale, lx_scale2;
+    double* terms;                             /* [2][GPI_REPLICAS]: logL_X, entropy of segment 1 */
+    double* terms2;                            /* the same of segment 2 */
+} gpi_gpmlp_desc;
+int gpi_gpmlp_forward(const gpi_gpmlp_desc* d, const float* params, float* ws, void* stream);
+int gpi_gpmlp_backward(const gpi_gpmlp_desc* d, const float* params, float* ws, double* gacc, void* stream);
+
+/* gpi_gp_sample with the MLP map (EffectivePropertyMap.propagate_samples components.py:238-249 and
+ * forward_mean): row r, j = r / rep, z = qz_mu[j] + exp(qz_ls[j]) eps_z (qz_ls NULL: z = qz_mu[j], nothing
+ * drawn), x = mlp(z) (+ exp(gp_ls) eps_x when gp_ls != NULL).  Normals and Philox streams as gpi_gp_sample.
+ * Plain device pointers; with qz_ls = gp_ls = NULL it is the surrogate predictor's deterministic gp mean.
+ * rows must be a multiple of rep; eps_z without qz_ls, or eps_x without gp_ls, is GPI_ERR_ARG. */
+typedef struct gpi_gpmlp_sample_desc {
+    int32_t rows, rep, n_layers;
+    int32_t width[GPI_GPMLP_MAX_HIDDEN + 2];
+    const float* qz_mu;
+    const float* qz_ls;
+    const float* w[GPI_GPMLP_MAX_HIDDEN + 1];
+    const float* b[GPI_GPMLP_MAX_HIDDEN + 1];
+    const float* gp_ls;
+    const float* eps_z;
+    const float* eps_x;
+    uint64_t seed;
+    const uint64_t* offset;
+    uint64_t sub;
+    float* x;                                  /* [rows, d_x] out */
+} gpi_gpmlp_sample_desc;
+int gpi_gpmlp_sample(const gpi_gpmlp_sample_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,10 +18,24 @@
 //   * nc = 4 / 8: rom_kernel_fast (Z = L^{-1} by one wave) and rom_lane_kernel; nc = 16: rom_kernel_fast<16> with
 //     the factorisation and the band sweeps by one wave whose lanes share the window (chol16_wave, band_sweep16)
 //     and rom16_coarse_kernel; any other nc <= 16, and GPI_ROM_SLOW=1: the barrier-per-step rom_kernel;
-//   * gpi_rom_fit (rom_fit_kernel, rom_fit16_kernel, below): OptimizeEffectiveProperties' whole Adam loop over x
+//   * gpi_rom_fit (rom_fit_kernel<4 | 8 | 16>, below): OptimizeEffectiveProperties' whole Adam loop over x
 //     in one launch.
+// Every kernel is put together from one statement of each block of the mathematics:
+//   kappa_of                    kappa from x, with the bad-value flag
+//   band_row                    one interior row of K and its right-hand side (c_h, c_v, Dirichlet lift of F),
+//                               returned as values; put_band_row stores it in the band layout L[ii * W + t]
+//   interior_node, u_node,      the interior <-> node index maps: u from (b, F), lambda from b with 0 on the
+//   lam_node                    Dirichlet nodes
+//   dk_edge, dx_of_dk           dJ/dkappa of a coarse triangle by the edge formula, and dJ/dx from it
+//   loglik_sum, gx_store        the workgroup's log-likelihood sum; dJ/dx per triangle into the gx row
+//   win_load, win_step,         the register-window Cholesky step and the substitutions' sliding window
+//   win_shift, win_row, h_push  (chol_band_seq, chol_inv_wave, solve_band_seq)
+//   fit_square_sums, fit_node_gather, fit_gu_row, adam_step, fit_update     the pieces of the fit
+// and every kernel family takes its dynamic-LDS carve-up and its launch size from one layout (rom_lds,
+// RomFastLds, Rom16CoarseLds, RomLaneLds, RomFitLds).
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 using namespace gpi;
 
@@ -53,23 +67,96 @@ struct RomDims {
     int nc, nn, nT, nI, bw, n, dy, r;
 };
 
-__device__ __forceinline__ float kap(const float* k, int nc, int I, int J, int ul) {
-    return k[2 * (I + nc * J) + ul];
+// kappa of one triangle from its x; `bad` collects the values that are not positive numbers (d.flag)
+__device__ __forceinline__ float kappa_of(float xv, bool input_kappa, bool& bad) {
+    const float kv = input_kappa ? xv : expf(xv) + 1e-8f;
+    bad |= !(kv > 1e-12f);
+    return kv;
 }
 
-// horizontal edge (I,J)-(I+1,J)
-__device__ __forceinline__ float c_h(const float* k, int nc, int I, int J) {
+// kappa accessor of band_row: triangle t -> kappa, from the LDS image kp[]
+struct LdsKappa {
+    const float* kp;
+    __device__ __forceinline__ float operator()(int t) const { return kp[t]; }
+};
+
+// horizontal edge (I,J)-(I+1,J); triangle (I, J, ul) is element 2 (I + nc J) + ul
+template <class K>
+__device__ __forceinline__ float c_h(const K& kap, int nc, int I, int J) {
     float c = 0.f;
-    if (J < nc) c += kap(k, nc, I, J, 0);
-    if (J > 0) c += kap(k, nc, I, J - 1, 1);
+    if (J < nc) c += kap(2 * (I + nc * J));
+    if (J > 0) c += kap(2 * (I + nc * (J - 1)) + 1);
     return 0.5f * c;
 }
 // vertical edge (I,J)-(I,J+1)
-__device__ __forceinline__ float c_v(const float* k, int nc, int I, int J) {
+template <class K>
+__device__ __forceinline__ float c_v(const K& kap, int nc, int I, int J) {
     float c = 0.f;
-    if (I > 0) c += kap(k, nc, I - 1, J, 0);
-    if (I < nc) c += kap(k, nc, I, J, 1);
+    if (I > 0) c += kap(2 * (I - 1 + nc * J));
+    if (I < nc) c += kap(2 * (I + nc * J) + 1);
     return 0.5f * c;
+}
+
+// Interior row ii of K (lower band) and of the right-hand side: the diagonal, the first and the (nc-1)-th
+// sub-diagonal, and F at the node with the Dirichlet neighbours lifted (rhs -= K_IB F_B).  Every kernel
+// stores these in its own layout.
+struct BandRow {
+    float dg, o1, on, rhs;
+};
+template <class K>
+__device__ __forceinline__ BandRow band_row(int nc, int ii, const float* F, const K& kap) {
+    const int J = ii / (nc - 1), I = ii - J * (nc - 1) + 1;
+    const int p = I + (nc + 1) * J;
+    const float chl = c_h(kap, nc, I - 1, J), chr = c_h(kap, nc, I, J);
+    const float cvd = J > 0 ? c_v(kap, nc, I, J - 1) : 0.f;
+    const float cvu = J < nc ? c_v(kap, nc, I, J) : 0.f;
+    BandRow r;
+    r.dg = chl + chr + cvd + cvu;
+    r.o1 = I - 1 >= 1 ? -chl : 0.f;
+    r.on = J >= 1 ? -cvd : 0.f;
+    r.rhs = F[p];
+    if (I - 1 == 0) r.rhs += chl * F[p - 1];
+    if (I + 1 == nc) r.rhs += chr * F[p + 1];
+    return r;
+}
+// ... in the band layout: row[t] = K(ii, ii - t), t < w = nc
+__device__ __forceinline__ void put_band_row(float* row, int w, const BandRow& r) {
+    for (int t = 0; t < w; ++t) row[t] = 0.f;
+    row[0] = r.dg;
+    row[1] += r.o1;
+    row[w - 1] += r.on;
+}
+
+// node of interior unknown ii (rows of nc - 1 interior nodes; the columns I = 0, nc are Dirichlet)
+__device__ __forceinline__ int interior_node(int nc, int ii) {
+    const int J = ii / (nc - 1), I = ii - J * (nc - 1) + 1;
+    return I + (nc + 1) * J;
+}
+__device__ __forceinline__ int interior_of(int nc, int I, int J) { return J * (nc - 1) + (I - 1); }
+// coarse solution at node e from the interior solution b and the boundary values F
+__device__ __forceinline__ float u_node(int nc, int e, const float* F, const float* b) {
+    const int I = e % (nc + 1), J = e / (nc + 1);
+    return (I == 0 || I == nc) ? F[e] : b[interior_of(nc, I, J)];
+}
+// its adjoint twin: lambda at node e, 0 on the Dirichlet nodes
+__device__ __forceinline__ float lam_node(int nc, int e, const float* b) {
+    const int I = e % (nc + 1), J = e / (nc + 1);
+    return (I == 0 || I == nc) ? 0.f : b[interior_of(nc, I, J)];
+}
+
+// dJ/dkappa_t of coarse triangle t (times 2): -(lambda_p - lambda_q)(u_p - u_q) over its two legs
+__device__ __forceinline__ float dk_edge(const float* lam, const float* u, int nc, int t) {
+    const int q = t >> 1, ul = t & 1;
+    const int I = q % nc, J = q / nc;
+    const int v0 = I + (nc + 1) * J, v1 = v0 + 1, v2 = v0 + (nc + 1), v3 = v2 + 1;
+    if (!ul)   // legs v0-v1 (bottom), v1-v3 (right)
+        return -(lam[v0] - lam[v1]) * (u[v0] - u[v1]) - (lam[v1] - lam[v3]) * (u[v1] - u[v3]);
+    // legs v2-v3 (top), v0-v2 (left)
+    return -(lam[v2] - lam[v3]) * (u[v2] - u[v3]) - (lam[v0] - lam[v2]) * (u[v0] - u[v2]);
+}
+// dJ/dx_t from it: dkappa/dx = exp(x) = kappa - 1e-8
+__device__ __forceinline__ float dx_of_dk(float dk, float kv, bool input_kappa) {
+    return 0.5f * dk * (input_kappa ? 1.f : (kv - 1e-8f));
 }
 
 __device__ void chol_band(float* L, const RomDims& D) {
@@ -125,34 +212,68 @@ __device__ void solve_band(const float* L, float* b, const RomDims& D) {
 // three workgroup barriers (78 -> ~10 us for the 63-unknown system at nc = 8).
 // dinv[k] = 1 / L(k,k) is kept for the solves, which run as partially unrolled loops (a full
 // unroll lets the scheduler hoist every band load and spill).
-template <int NC>
-__device__ __forceinline__ void chol_band_seq(float* __restrict__ L, float* __restrict__ dinv) {
-    constexpr int W = NC, NI = (NC - 1) * (NC + 1);
-    float win[W][W];   // win[a][t] = L(k + a, k + a - t)
+// The window win[a][t] = L(k + a, k + a - t) and its moves, shared by chol_band_seq, chol_inv_wave and
+// (written out once more in) rom_lane_kernel.
+// row k of the band (zero past the end)
+template <int W>
+__device__ __forceinline__ void win_row(float (&row)[W], const float* L, int k, int NI) {
+#pragma unroll
+    for (int t = 0; t < W; ++t) row[t] = (k < NI) ? L[k * W + t] : 0.f;
+}
+template <int W>
+__device__ __forceinline__ void win_load(float (&win)[W][W], const float* L, int NI) {
 #pragma unroll
     for (int a = 0; a < W; ++a)
 #pragma unroll
         for (int t = 0; t < W; ++t) win[a][t] = a < NI ? L[a * W + t] : 0.f;
+}
+// factorisation step k with inv = 1 / L(k,k): scale column k, rank-1 update of the trailing window
+template <int W>
+__device__ __forceinline__ void win_step(float (&win)[W][W], float inv) {
+#pragma unroll
+    for (int a = 1; a < W; ++a) win[a][a] *= inv;                       // L(k+a, k)
+#pragma unroll
+    for (int a = 1; a < W; ++a)
+#pragma unroll
+        for (int b = 1; b <= a; ++b) win[a][a - b] = fmaf(-win[a][a], win[b][b], win[a][a - b]);
+}
+// row k leaves: rows move up (register renaming), the caller refills win[W - 1]
+template <int W>
+__device__ __forceinline__ void win_shift(float (&win)[W][W]) {
+#pragma unroll
+    for (int a = 0; a + 1 < W; ++a)
+#pragma unroll
+        for (int t = 0; t < W; ++t) win[a][t] = win[a + 1][t];
+}
+// the substitutions' sliding window of the last BW values: h[t-1] = y[k - t] (forward), x[k + t] (backward)
+template <int BW>
+__device__ __forceinline__ void h_clear(float (&h)[BW]) {
+#pragma unroll
+    for (int t = 0; t < BW; ++t) h[t] = 0.f;
+}
+template <int BW>
+__device__ __forceinline__ void h_push(float (&h)[BW], float a) {
+#pragma unroll
+    for (int t = BW - 1; t > 0; --t) h[t] = h[t - 1];
+    h[0] = a;
+}
+
+template <int NC>
+__device__ __forceinline__ void chol_band_seq(float* __restrict__ L, float* __restrict__ dinv) {
+    constexpr int W = NC, NI = (NC - 1) * (NC + 1);
+    float win[W][W];
+    win_load<W>(win, L, NI);
 #pragma unroll
     for (int k = 0; k < NI; ++k) {
         const float dk = sqrtf(win[0][0]);
         const float inv = 1.f / dk;
         win[0][0] = dk;
         dinv[k] = inv;
-#pragma unroll
-        for (int a = 1; a < W; ++a) win[a][a] *= inv;                       // L(k+a, k)
-#pragma unroll
-        for (int a = 1; a < W; ++a)
-#pragma unroll
-            for (int b = 1; b <= a; ++b) win[a][a - b] = fmaf(-win[a][a], win[b][b], win[a][a - b]);
+        win_step<W>(win, inv);
 #pragma unroll
         for (int t = 0; t < W; ++t) L[k * W + t] = win[0][t];
-#pragma unroll
-        for (int a = 0; a + 1 < W; ++a)
-#pragma unroll
-            for (int t = 0; t < W; ++t) win[a][t] = win[a + 1][t];
-#pragma unroll
-        for (int t = 0; t < W; ++t) win[W - 1][t] = (k + W < NI) ? L[(k + W) * W + t] : 0.f;
+        win_shift<W>(win);
+        win_row<W>(win[W - 1], L, k + W, NI);
     }
 }
 
@@ -161,9 +282,8 @@ template <int NC>
 __device__ __forceinline__ void solve_band_seq(const float* __restrict__ L, const float* __restrict__ dinv,
                                                float* __restrict__ b) {
     constexpr int BW = NC - 1, W = NC, NI = (NC - 1) * (NC + 1);
-    float h[BW];   // sliding window of the last BW solution values (h[t-1] = y[k - t])
-#pragma unroll
-    for (int t = 0; t < BW; ++t) h[t] = 0.f;
+    float h[BW];
+    h_clear(h);
 #pragma unroll 8
     for (int k = 0; k < NI; ++k) {
         float a = b[k];
@@ -172,12 +292,9 @@ __device__ __forceinline__ void solve_band_seq(const float* __restrict__ L, cons
             if (k - t >= 0) a = fmaf(-L[k * W + t], h[t - 1], a);
         a *= dinv[k];
         b[k] = a;
-#pragma unroll
-        for (int t = BW - 1; t > 0; --t) h[t] = h[t - 1];
-        h[0] = a;
+        h_push(h, a);
     }
-#pragma unroll
-    for (int t = 0; t < BW; ++t) h[t] = 0.f;        // h[t-1] = x[k + t]
+    h_clear(h);
 #pragma unroll 8
     for (int k = NI - 1; k >= 0; --k) {
         float a = b[k];
@@ -186,9 +303,7 @@ __device__ __forceinline__ void solve_band_seq(const float* __restrict__ L, cons
             if (k + t < NI) a = fmaf(-L[(k + t) * W + t], h[t - 1], a);
         a *= dinv[k];
         b[k] = a;
-#pragma unroll
-        for (int t = BW - 1; t > 0; --t) h[t] = h[t - 1];
-        h[0] = a;
+        h_push(h, a);
     }
 }
 
@@ -213,17 +328,56 @@ constexpr int ROM_U = 8;         // fine nodes per batch of global loads
 #define GPI_ROM_FAST_NT_DEFAULT 512
 #endif
 
+// the workgroup's log-likelihood: per-wave sums through lred[NW], in wave order, into the sample's replica
+template <int NW>
+__device__ __forceinline__ void loglik_sum(const gpi_rom_desc& d, float Lsum, double* lred) {
+    const int tid = threadIdx.x;
+    Lsum = wave_sum(Lsum);
+    if ((tid & 63) == 0) lred[tid >> 6] = (double)Lsum;
+    __syncthreads();
+    if (tid == 0 && d.loss_acc) {
+        double t = lred[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) t += lred[w];
+        atomicAdd(d.loss_acc + blockIdx.x % GPI_REPLICAS, t);
+    }
+}
+// dJ/dx per coarse triangle into the sample's gx row (NT threads)
+template <int NT>
+__device__ __forceinline__ void gx_store(const gpi_rom_desc& d, int s, int nc, int nT, const float* lam,
+                                         const float* u, const float* kp) {
+    for (int t = threadIdx.x; t < nT; t += NT) {
+        const float g = dx_of_dk(dk_edge(lam, u, nc, t), kp[t], d.input_kappa);
+        float* gp = d.gx + (int64_t)s * d.gx_stride + t;
+        *gp = (d.gx_accumulate ? *gp : 0.f) + g;
+    }
+}
+
+// rom_kernel's dynamic LDS: float offsets (the fp64 block at an even one) and the launch size
+struct RomLds {
+    int kp, L, u, b, lam, du, lred, dinv;
+    size_t bytes;
+};
+__host__ __device__ __forceinline__ RomLds rom_lds(const RomDims& D) {
+    RomLds o;
+    o.kp = 0;                              // [nT] kappa
+    o.L = o.kp + D.nT;                     // [nI * w]
+    o.u = o.L + D.nI * (D.bw + 1);         // [nn]
+    o.b = o.u + D.nn;                      // [nI]
+    o.lam = o.b + D.nI;                    // [nn]
+    const int fl = o.lam + D.nn;
+    o.du = (fl + 1) & ~1;                  // [nn] fp64 W^T dmu
+    o.lred = o.du + 2 * D.nn;              // [ROM_NT / 64] fp64 per-wave log-likelihood sums
+    o.dinv = o.lred + 2 * (ROM_NT / 64);   // [nI] 1 / L(k,k) (nc = 4, 8 path)
+    o.bytes = sizeof(float) * (fl + 4 + 2 * D.nn + 2 * (ROM_NT / 64) + D.nI);   // 4 floats of alignment slack
+    return o;
+}
+
 __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int w = D.bw + 1;
-    float* kp = sm;                   // [nT] kappa
-    float* L = kp + D.nT;             // [nI * w]
-    float* u = L + D.nI * w;          // [nn]
-    float* b = u + D.nn;              // [nI]
-    float* lam = b + D.nI;            // [nn]
-    double* du = (double*)(sm + ((D.nT + D.nI * w + 2 * D.nn + D.nI + 1) & ~1));   // [nn] fp64 W^T dmu
-    double* lred = du + D.nn;         // [ROM_NT / 64] per-wave log-likelihood sums
-    float* dinv = (float*)(lred + ROM_NT / 64);   // [nI] 1 / L(k,k) (nc = 4, 8 path)
+    const RomLds o = rom_lds(D);
+    float *kp = sm + o.kp, *L = sm + o.L, *u = sm + o.u, *b = sm + o.b, *lam = sm + o.lam, *dinv = sm + o.dinv;
+    double *du = (double*)(sm + o.du), *lred = (double*)(sm + o.lred);
     const int s = blockIdx.x;
     const int tid = threadIdx.x, NT = ROM_NT;
     const int nc = D.nc;
@@ -231,12 +385,7 @@ __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) 
     RPHASE(0);
 
     bool bad = false;
-    for (int t = tid; t < D.nT; t += NT) {
-        const float xv = rom_x(d, s, t);
-        const float kv = d.input_kappa ? xv : expf(xv) + 1e-8f;
-        bad |= !(kv > 1e-12f);
-        kp[t] = kv;
-    }
+    for (int t = tid; t < D.nT; t += NT) kp[t] = kappa_of(rom_x(d, s, t), d.input_kappa, bad);
     if (bad && d.flag) atomicOr(d.flag, 1);
     for (int e = tid; e < D.nn; e += NT) {
         du[e] = (d.mode == GPI_ROM_BACKWARD && d.duc) ? (double)d.duc[(int64_t)s * D.nn + e] : 0.0;
@@ -246,20 +395,9 @@ __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) 
 
     // ---- assemble interior system (banded lower) + rhs
     for (int ii = tid; ii < D.nI; ii += NT) {
-        const int J = ii / (nc - 1), I = ii - J * (nc - 1) + 1;
-        const int p = I + (nc + 1) * J;
-        const float chl = c_h(kp, nc, I - 1, J), chr = c_h(kp, nc, I, J);
-        const float cvd = J > 0 ? c_v(kp, nc, I, J - 1) : 0.f;
-        const float cvu = J < nc ? c_v(kp, nc, I, J) : 0.f;
-        float* row = L + ii * w;
-        for (int t = 0; t < w; ++t) row[t] = 0.f;
-        row[0] = chl + chr + cvd + cvu;
-        if (I - 1 >= 1) row[1] += -chl;
-        if (J >= 1) row[D.bw] += -cvd;
-        float rhs = F[p];
-        if (I - 1 == 0) rhs += chl * F[p - 1];
-        if (I + 1 == nc) rhs += chr * F[p + 1];
-        b[ii] = rhs;
+        const BandRow row = band_row(nc, ii, F, LdsKappa{kp});
+        put_band_row(L + ii * nc, nc, row);
+        b[ii] = row.rhs;
     }
     __syncthreads();
     RPHASE(1);
@@ -273,10 +411,7 @@ __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) 
         chol_band(L, D);
         solve_band(L, b, D);
     }
-    for (int e = tid; e < D.nn; e += NT) {
-        const int I = e % (nc + 1), J = e / (nc + 1);
-        u[e] = (I == 0 || I == nc) ? F[e] : b[J * (nc - 1) + (I - 1)];
-    }
+    for (int e = tid; e < D.nn; e += NT) u[e] = u_node(nc, e, F, b);
     __syncthreads();
     RPHASE(2);
     if (d.uc) for (int e = tid; e < D.nn; e += NT) d.uc[(int64_t)s * D.nn + e] = u[e];
@@ -366,26 +501,13 @@ __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) 
             }
         }
     }
-    if (d.mode == GPI_ROM_LOGLIK) {
-        Lsum = wave_sum(Lsum);
-        if ((tid & 63) == 0) lred[tid >> 6] = (double)Lsum;
-        __syncthreads();
-        if (tid == 0 && d.loss_acc) {
-            double t = lred[0];
-#pragma unroll
-            for (int w = 1; w < ROM_NT / 64; ++w) t += lred[w];
-            atomicAdd(d.loss_acc + blockIdx.x % GPI_REPLICAS, t);
-        }
-    }
+    if (d.mode == GPI_ROM_LOGLIK) loglik_sum<ROM_NT / 64>(d, Lsum, lred);
     if (d.mode == GPI_ROM_FORWARD) return;
     __syncthreads();
     RPHASE(3);
 
     // ---- adjoint
-    for (int ii = tid; ii < D.nI; ii += NT) {
-        const int J = ii / (nc - 1), I = ii - J * (nc - 1) + 1;
-        b[ii] = (float)du[I + (nc + 1) * J];
-    }
+    for (int ii = tid; ii < D.nI; ii += NT) b[ii] = (float)du[interior_node(nc, ii)];
     __syncthreads();
     if (nc == 8 || nc == 4) {
         if (tid == 0) {
@@ -397,26 +519,9 @@ __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) 
         solve_band(L, b, D);
     }
     RPHASE(4);
-    for (int ii = tid; ii < D.nI; ii += NT) {
-        const int J = ii / (nc - 1), I = ii - J * (nc - 1) + 1;
-        lam[I + (nc + 1) * J] = b[ii];
-    }
+    for (int ii = tid; ii < D.nI; ii += NT) lam[interior_node(nc, ii)] = b[ii];
     __syncthreads();
-    // ---- dJ/dx per coarse triangle
-    for (int t = tid; t < D.nT; t += NT) {
-        const int q = t >> 1, ul = t & 1;
-        const int I = q % nc, J = q / nc;
-        const int v0 = I + (nc + 1) * J, v1 = v0 + 1, v2 = v0 + (nc + 1), v3 = v2 + 1;
-        float dk;
-        if (!ul) {   // legs v0-v1 (bottom), v1-v3 (right)
-            dk = -(lam[v0] - lam[v1]) * (u[v0] - u[v1]) - (lam[v1] - lam[v3]) * (u[v1] - u[v3]);
-        } else {     // legs v2-v3 (top), v0-v2 (left)
-            dk = -(lam[v2] - lam[v3]) * (u[v2] - u[v3]) - (lam[v0] - lam[v2]) * (u[v0] - u[v2]);
-        }
-        const float g = 0.5f * dk * (d.input_kappa ? 1.f : (kp[t] - 1e-8f));
-        float* gp = d.gx + (int64_t)s * d.gx_stride + t;
-        *gp = (d.gx_accumulate ? *gp : 0.f) + g;
-    }
+    gx_store<ROM_NT>(d, s, nc, D.nT, lam, u, kp);
     RPHASE(5);
 }
 
@@ -449,19 +554,13 @@ template <int NC>
 __device__ __forceinline__ void chol_inv_wave(const float* __restrict__ L, float* __restrict__ z) {
     constexpr int W = NC, BW = NC - 1, NI = (NC - 1) * (NC + 1);
     const int j = threadIdx.x & 63;
-    float win[W][W];   // win[a][t] = L(k + a, k + a - t)
+    float win[W][W];
     float nxt[2][W];   // rows k + W, k + W + 1 (prefetched)
-#pragma unroll
-    for (int a = 0; a < W; ++a)
-#pragma unroll
-        for (int t = 0; t < W; ++t) win[a][t] = a < NI ? L[a * W + t] : 0.f;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int t = 0; t < W; ++t) nxt[u][t] = (W + u < NI) ? L[(W + u) * W + t] : 0.f;
+    win_load<W>(win, L, NI);
+    win_row<W>(nxt[0], L, W, NI);
+    win_row<W>(nxt[1], L, W + 1, NI);
     float h[BW];       // h[t-1] = y[k - t] of this lane's right-hand side e_j
-#pragma unroll
-    for (int t = 0; t < BW; ++t) h[t] = 0.f;
+    h_clear(h);
 #pragma unroll
     for (int k = 0; k < NI; ++k) {
         const float inv = __builtin_amdgcn_rsqf(win[0][0]);
@@ -475,20 +574,10 @@ __device__ __forceinline__ void chol_inv_wave(const float* __restrict__ L, float
         }
         y = (y + y2) * inv;
         z[k * KINV_P + j] = y;
-#pragma unroll
-        for (int t = BW - 1; t > 0; --t) h[t] = h[t - 1];
-        h[0] = y;
+        h_push(h, y);
         // factorisation step k
-#pragma unroll
-        for (int a = 1; a < W; ++a) win[a][a] *= inv;                       // L(k+a, k)
-#pragma unroll
-        for (int a = 1; a < W; ++a)
-#pragma unroll
-            for (int b = 1; b <= a; ++b) win[a][a - b] = fmaf(-win[a][a], win[b][b], win[a][a - b]);
-#pragma unroll
-        for (int a = 0; a + 1 < W; ++a)
-#pragma unroll
-            for (int t = 0; t < W; ++t) win[a][t] = win[a + 1][t];
+        win_step<W>(win, inv);
+        win_shift<W>(win);
 #pragma unroll
         for (int t = 0; t < W; ++t) {
             win[W - 1][t] = nxt[0][t];
@@ -681,26 +770,30 @@ __device__ __forceinline__ void band_sweep16(const float* __restrict__ Lb, float
 // NT threads per sample (256 / 512 / 1024): SUB = NT / 64 threads share one coarse square of the
 // prolongation (nc = 8: 64 squares; nc = 4 uses 16 of them), so a wider workgroup has more waves in flight
 // over the 4095 fine nodes; the factorisation stays in wave 0.
-template <int NC>
-constexpr int rom_fast_factor_floats() {
-    return NC == 16 ? R16_LR + R16_LC : (NC - 1) * (NC + 1) * KINV_P;
-}
+template <int NC, int NT>
+struct RomFastLds {   // float offsets; the fp64 block (du [NN], lred [NW]) at the even offset DU
+    static constexpr int W = NC, NI = (NC - 1) * (NC + 1), NN = (NC + 1) * (NC + 1), NT2 = 2 * NC * NC, NW = NT / 64;
+    static constexpr int FACTOR = NC == 16 ? R16_LR + R16_LC : NI * KINV_P;   // Lr, Lc of chol16_wave / Z = L^{-1}
+    // (DINV: NI floats no kernel reads any more, kept so that the size and every offset stay what they were)
+    static constexpr int KP = 0, L = KP + NT2, U = L + NI * W, B = U + NN, LAM = B + NI, DINV = LAM + NN,
+                         KINV = DINV + NI, PART = KINV + FACTOR, DU = (PART + 64 * NW + 64 + 1) & ~1;
+    static constexpr size_t bytes = sizeof(float) * DU + sizeof(double) * (NN + NW);
+};
 
 template <int NC, int NT>
 __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D) {
-    constexpr int W = NC, BW = NC - 1, NI = (NC - 1) * (NC + 1), NN = (NC + 1) * (NC + 1), NT2 = 2 * NC * NC;
-    constexpr int SUB = NT / 64, NW = NT / 64;
+    using S = RomFastLds<NC, NT>;
+    constexpr int NI = S::NI, NN = S::NN, NT2 = S::NT2, SUB = NT / 64, NW = S::NW;
     constexpr int PF = (SUB >= 8 ? 1 : 3) * ROM_U;   // prefetched fine nodes per thread (a square holds <= (r+1) r)
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* kp = sm;                   // [NT2] kappa
-    float* L = kp + NT2;              // [NI * W]
-    float* u = L + NI * W;            // [NN]
-    float* b = u + NN;                // [NI]
-    float* lam = b + NI;              // [NN]
-    float* dinv = lam + NN;           // [NI]
-    float* kinv = dinv + NI;          // [NI][KINV_P]: Z = L^{-1} (NC = 16: Lr, then Lc of chol16_wave)
-    float* part = kinv + rom_fast_factor_floats<NC>(); // [64 NW + 64] kinv_apply scratch
-    double* du = (double*)(sm + ((NT2 + NI * W + 2 * NN + 2 * NI + rom_fast_factor_floats<NC>() + 64 * NW + 64 + 1) & ~1));   // [NN]
+    float* kp = sm + S::KP;           // [NT2] kappa
+    float* L = sm + S::L;             // [NI * W]
+    float* u = sm + S::U;             // [NN]
+    float* b = sm + S::B;             // [NI]
+    float* lam = sm + S::LAM;         // [NN]
+    float* kinv = sm + S::KINV;       // [NI][KINV_P]: Z = L^{-1} (NC = 16: Lr, then Lc of chol16_wave)
+    float* part = sm + S::PART;       // [64 NW + 64] kinv_apply scratch
+    double* du = (double*)(sm + S::DU);   // [NN]
     double* lred = du + NN;           // [NW]
     const int s = blockIdx.x;
     const int tid = threadIdx.x;
@@ -729,12 +822,7 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
         }
     }
     bool bad = false;
-    for (int t = tid; t < NT2; t += NT) {
-        const float xv = rom_x(d, s, t);
-        const float kv = d.input_kappa ? xv : expf(xv) + 1e-8f;
-        bad |= !(kv > 1e-12f);
-        kp[t] = kv;
-    }
+    for (int t = tid; t < NT2; t += NT) kp[t] = kappa_of(rom_x(d, s, t), d.input_kappa, bad);
     if (bad && d.flag) atomicOr(d.flag, 1);
     for (int e = tid; e < NN; e += NT) {
         du[e] = (d.mode == GPI_ROM_BACKWARD && d.duc) ? (double)d.duc[(int64_t)s * NN + e] : 0.0;
@@ -743,21 +831,9 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
     __syncthreads();
     // ---- assemble the interior system (banded lower) + rhs
     for (int ii = tid; ii < NI; ii += NT) {
-        const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
-        const int p = I + (NC + 1) * J;
-        const float chl = c_h(kp, NC, I - 1, J), chr = c_h(kp, NC, I, J);
-        const float cvd = J > 0 ? c_v(kp, NC, I, J - 1) : 0.f;
-        const float cvu = J < NC ? c_v(kp, NC, I, J) : 0.f;
-        float* row = L + ii * W;
-#pragma unroll
-        for (int t = 0; t < W; ++t) row[t] = 0.f;
-        row[0] = chl + chr + cvd + cvu;
-        if (I - 1 >= 1) row[1] += -chl;
-        if (J >= 1) row[BW] += -cvd;
-        float rhs = F[p];
-        if (I - 1 == 0) rhs += chl * F[p - 1];
-        if (I + 1 == NC) rhs += chr * F[p + 1];
-        b[ii] = rhs;
+        const BandRow row = band_row(NC, ii, F, LdsKappa{kp});
+        put_band_row(L + ii * NC, NC, row);
+        b[ii] = row.rhs;
     }
     __syncthreads();
     RPHASE(1);
@@ -768,7 +844,7 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
     if constexpr (NC == 16) {
         // wave 0: band factorisation with the forward substitution of b riding along, then the back sweep
         if (tid < 64) {
-            const Band16 A = {L, L + 1, L + BW, W};
+            const Band16 A = {L, L + 1, L + NC - 1, NC};
             chol16_wave(A, kinv, kinv + R16_LR, b);
             RPHASE(6);
             band_sweep16<false>(kinv, b);
@@ -784,14 +860,12 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
         kinv_apply<NC, NT>(kinv, b, part, b);
     }
     RPHASE(2);
-    for (int e = tid; e < NN; e += NT) {
-        const int I = e % (NC + 1), J = e / (NC + 1);
-        u[e] = (I == 0 || I == NC) ? F[e] : b[J * (NC - 1) + (I - 1)];
-    }
+    for (int e = tid; e < NN; e += NT) u[e] = u_node(NC, e, F, b);
     __syncthreads();
     if (d.uc) for (int e = tid; e < NN; e += NT) d.uc[(int64_t)s * NN + e] = u[e];
 
-    // ---- prolongation (+ log-likelihood, + W^T of the output gradient), as rom_kernel; the first
+    // ---- prolongation (+ log-likelihood, + W^T of the output gradient), rom_kernel's loop with SUB threads per
+    // coarse square, e / ncol by umulhi (exact for e < 2^16, which these shapes guarantee), and the first
     // PF nodes of every thread's square from the entry prefetch
     const float rinv = 1.f / (float)r;
     float Lsum = 0.f;
@@ -887,25 +961,12 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
         }
     }
     RPHASE(7);
-    if (d.mode == GPI_ROM_LOGLIK) {
-        Lsum = wave_sum(Lsum);
-        if ((tid & 63) == 0) lred[tid >> 6] = (double)Lsum;
-        __syncthreads();
-        if (tid == 0 && d.loss_acc) {
-            double t = lred[0];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) t += lred[w];
-            atomicAdd(d.loss_acc + blockIdx.x % GPI_REPLICAS, t);
-        }
-    }
+    if (d.mode == GPI_ROM_LOGLIK) loglik_sum<NW>(d, Lsum, lred);
     if (d.mode == GPI_ROM_FORWARD) return;
     __syncthreads();
     RPHASE(3);
     // ---- adjoint lambda = K^{-1} (W^T dmu)_interior = Z^T (Z r)
-    for (int ii = tid; ii < NI; ii += NT) {
-        const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
-        b[ii] = (float)du[I + (NC + 1) * J];
-    }
+    for (int ii = tid; ii < NI; ii += NT) b[ii] = (float)du[interior_node(NC, ii)];
     __syncthreads();
     if constexpr (NC == 16) {
         if (tid < 64) {
@@ -916,32 +977,11 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
     } else {
         kinv_apply<NC, NT>(kinv, b, part, b);
     }
-    for (int ii = tid; ii < NI; ii += NT) {
-        const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
-        lam[I + (NC + 1) * J] = b[ii];
-    }
+    for (int ii = tid; ii < NI; ii += NT) lam[interior_node(NC, ii)] = b[ii];
     __syncthreads();
     RPHASE(4);
-    // ---- dJ/dx per coarse triangle
-    for (int t = tid; t < NT2; t += NT) {
-        const int q = t >> 1, ul = t & 1;
-        const int I = q % NC, J = q / NC;
-        const int v0 = I + (NC + 1) * J, v1 = v0 + 1, v2 = v0 + (NC + 1), v3 = v2 + 1;
-        float dk;
-        if (!ul) dk = -(lam[v0] - lam[v1]) * (u[v0] - u[v1]) - (lam[v1] - lam[v3]) * (u[v1] - u[v3]);
-        else dk = -(lam[v2] - lam[v3]) * (u[v2] - u[v3]) - (lam[v0] - lam[v2]) * (u[v0] - u[v2]);
-        const float g = 0.5f * dk * (d.input_kappa ? 1.f : (kp[t] - 1e-8f));
-        float* gp = d.gx + (int64_t)s * d.gx_stride + t;
-        *gp = (d.gx_accumulate ? *gp : 0.f) + g;
-    }
+    gx_store<NT>(d, s, NC, NT2, lam, u, kp);
     RPHASE(5);
-}
-
-template <int NC, int NT>
-size_t rom_fast_lds() {
-    constexpr int W = NC, NI = (NC - 1) * (NC + 1), NN = (NC + 1) * (NC + 1), NT2 = 2 * NC * NC, NW = NT / 64;
-    const size_t fl = ((NT2 + NI * W + 2 * NN + 2 * NI + rom_fast_factor_floats<NC>() + 64 * NW + 64 + 1) & ~1);
-    return sizeof(float) * fl + sizeof(double) * (NN + NW);
 }
 
 // Coarse solutions only at nc = 16: ONE WAVE PER SAMPLE, R16C_SPW samples per workgroup (the waves never
@@ -949,69 +989,69 @@ size_t rom_fast_lds() {
 // assembles its system as three diagonals, factors it with the forward substitution riding along
 // (chol16_wave, no Lc: no forward sweep follows) and runs the one back sweep.
 constexpr int R16C_SPW = 2;
-constexpr int R16C_FLOATS = 512 + 4 * 256 + R16_LR;   // kappa, diagonal / sub-diagonals / rhs, Lr (per wave)
+struct Rom16CoarseLds {   // float offsets within a wave's block
+    static constexpr int KP = 0, DG = KP + 512, O1 = DG + 256, O15 = O1 + 256, B = O15 + 256, LR = B + 256,
+                         FLOATS = LR + R16_LR;
+    static constexpr size_t bytes = sizeof(float) * R16C_SPW * FLOATS;
+};
 
 __global__ __launch_bounds__(64 * R16C_SPW) void rom16_coarse_kernel(gpi_rom_desc d) {
+    using S = Rom16CoarseLds;
     constexpr int NC = 16, NN = 289, NT2 = 512;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * R16C_SPW + (threadIdx.x >> 6);
     if (s >= d.n) return;
-    float* kp = sm + (threadIdx.x >> 6) * R16C_FLOATS;   // [512]
-    float* dg = kp + NT2;                                 // [256] each
-    float* o1 = dg + 256;
-    float* o15 = o1 + 256;
-    float* b = o15 + 256;
-    float* Lr = b + 256;                                  // [R16_LR]
+    float* base = sm + (threadIdx.x >> 6) * S::FLOATS;          // this wave's block
+    float* kp = base + S::KP;                                   // [512] kappa
+    float* dg = base + S::DG;                                   // [256] each: diagonal, sub-diagonals, rhs
+    float* o1 = base + S::O1;
+    float* o15 = base + S::O15;
+    float* b = base + S::B;
+    float* Lr = base + S::LR;                                   // [R16_LR]
     const float* __restrict__ F = d.F + (int64_t)s * NN;
     bool bad = false;
 #pragma unroll
-    for (int t = lane; t < NT2; t += 64) {
-        const float xv = rom_x(d, s, t);
-        const float kv = d.input_kappa ? xv : expf(xv) + 1e-8f;
-        bad |= !(kv > 1e-12f);
-        kp[t] = kv;
-    }
+    for (int t = lane; t < NT2; t += 64) kp[t] = kappa_of(rom_x(d, s, t), d.input_kappa, bad);
     if (bad && d.flag) atomicOr(d.flag, 1);
     wave_sync();
 #pragma unroll
     for (int ii = lane; ii < R16_NI; ii += 64) {
-        const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
-        const int p = I + (NC + 1) * J;
-        const float chl = c_h(kp, NC, I - 1, J), chr = c_h(kp, NC, I, J);
-        const float cvd = J > 0 ? c_v(kp, NC, I, J - 1) : 0.f;
-        const float cvu = J < NC ? c_v(kp, NC, I, J) : 0.f;
-        dg[ii] = chl + chr + cvd + cvu;
-        o1[ii] = I - 1 >= 1 ? -chl : 0.f;
-        o15[ii] = J >= 1 ? -cvd : 0.f;
-        float rhs = F[p];
-        if (I - 1 == 0) rhs += chl * F[p - 1];
-        if (I + 1 == NC) rhs += chr * F[p + 1];
-        b[ii] = rhs;
+        const BandRow row = band_row(NC, ii, F, LdsKappa{kp});
+        dg[ii] = row.dg;
+        o1[ii] = row.o1;
+        o15[ii] = row.on;
+        b[ii] = row.rhs;
     }
     wave_sync();
     const Band16 A = {dg, o1, o15, 1};
     chol16_wave(A, Lr, nullptr, b);
     band_sweep16<false>(Lr, b);
     float* uc = d.uc + (int64_t)s * NN;
-    for (int e = lane; e < NN; e += 64) {
-        const int I = e % (NC + 1), J = e / (NC + 1);
-        uc[e] = (I == 0 || I == NC) ? F[e] : b[J * (NC - 1) + (I - 1)];
-    }
+    for (int e = lane; e < NN; e += 64) uc[e] = u_node(NC, e, F, b);
 }
 
 // Coarse solutions only (FORWARD without mu_y: the VO MC predictive, N_vo x N_mc samples), nc = 4 / 8:
 // ONE LANE PER SAMPLE.  rom_kernel runs the banded Cholesky in one lane of a 256-thread workgroup per
 // sample; here every lane of a wave64 factors its own sample's system with the same register window
-// (chol_band_seq), the forward substitution fused into the factorisation (row k of L is final when
-// the window reaches it) and the band rows / right-hand side in LDS interleaved by lane ([entry][64]:
-// conflict-free).  Slot 0 of each stored L row holds 1 / L(k,k).
+// (chol_band_seq), the forward substitution fused into the factorisation (row k of L is final when the window
+// reaches it) and the band rows / right-hand side in LDS interleaved by lane ([entry][64]: conflict-free).
+// Slot 0 of each stored L row holds 1 / L(k,k).  This kernel keeps its own statement of the band row, the window
+// step and the back substitution: its 63 fully unrolled steps compile to other code, and a measurably slower
+// solve, through every form of the shared helpers that was tried (profiles/rom_refactor_isa.txt).
+template <int NC>
+struct RomLaneLds {   // float offsets
+    static constexpr int W = NC, NI = (NC - 1) * (NC + 1);
+    static constexpr int LS = 0, BS = LS + NI * W * 64;          // [NI * W][64], [NI][64]
+    static constexpr size_t bytes = sizeof(float) * (BS + NI * 64);
+};
+
 template <int NC>
 __global__ __launch_bounds__(64) void rom_lane_kernel(gpi_rom_desc d) {
     constexpr int W = NC, BW = NC - 1, NI = (NC - 1) * (NC + 1), NN = (NC + 1) * (NC + 1);
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* Ls = sm;                       // [NI * W][64]
-    float* Bs = sm + NI * W * 64;         // [NI][64]
+    float* Ls = sm + RomLaneLds<NC>::LS;  // [NI * W][64]
+    float* Bs = sm + RomLaneLds<NC>::BS;  // [NI][64]
     const int lane = threadIdx.x;
     const int s = blockIdx.x * 64 + lane;
     const bool act = s < d.n;
@@ -1122,19 +1162,24 @@ __global__ __launch_bounds__(64) void rom_lane_kernel(gpi_rom_desc d) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// rom_fit_kernel<NC> (gpi_rom_fit; nc = 4 / 8): ONE WAVE64 PER SAMPLE runs every Adam iteration of
+// rom_fit_kernel<NC> (gpi_rom_fit; nc = 4 / 8 / 16): ONE WAVE64 PER SAMPLE runs every Adam iteration of
 // OptimizeEffectiveProperties (bottleneck/utils.py:250-282) in one launch.  Row n of the gradient
 // depends on row n alone (the MSE mean's 1 / (n_total d_y) is a constant), so the workgroups never talk.
-//   setup      one pass over Y_n: lane q owns coarse square q (interp()'s partition of the fine free
-//              nodes) and sums, in fp64 and in a fixed order, its nodes' shares of b_n = W^T Y_n,
-//              c_n = |Y_n|^2 and G = W^T W (per square: 4 diagonal and 5 edge entries -- the "/"
-//              triangles never couple a square's +x and +y corners, hence <= 7 non-zeros per row);
-//              the squares' shares meet per coarse node in LDS (gather, fixed order: no atomics).
-//   iteration  kappa = exp(x) + 1e-8 -> band rows -> chol_inv_wave (Z = L^{-1}) -> u = Z^T (Z rhs) ->
-//              fp64: G u, ss = u^T (G u - 2 b) + c, g_u = gscale (G u - b) -> lambda = Z^T (Z g_u) ->
-//              dJ/dx by the edge formula of rom_kernel -> adam_element on the lane's x, m, v.
+//   setup      one pass over Y_n: a lane owns the coarse squares q = lane + 64 k (in that order: c_n's partial
+//              is one chain per lane; interp()'s partition of the fine free nodes) and sums, in fp64 and in a
+//              fixed order, its nodes' shares of b_n = W^T Y_n, c_n = |Y_n|^2 and G = W^T W (fit_square_sums;
+//              per square: 4 diagonal and 5 edge entries -- the "/" triangles never couple a square's +x and
+//              +y corners, hence <= 7 non-zeros per row); the squares' shares meet per coarse node in LDS
+//              (fit_node_gather, fixed order: no atomics).  They are staged over the solver's factor storage,
+//              which is free until the first iteration.
+//   iteration  kappa = exp(x) + 1e-8 -> band_row -> the solver's factorisation and u = K^{-1} rhs ->
+//              fp64: G u (fit_gu_row), ss = u^T (G u - 2 b) + c, g_u = gscale (G u - b) -> lambda = K^{-1} g_u
+//              -> dJ/dx by dk_edge -> adam_element on the lane's x, m, v (fit_update).
 // x, m, v live in registers (triangle t = lane + 64 k); an iteration touches coarse quantities only, its
 // cost does not depend on the refinement.  No cross-workgroup traffic, no waits.
+// The solver (FitSolverZ at nc = 4 / 8, FitSolver16 at nc = 16) brings its scratch layout, the storage the
+// row assembly writes to, the two solves and its synchronisation primitive: the workgroup is one wave, and
+// every LDS hand-off between lanes is followed by the solver's sync().
 
 // out = Z^T (Z v) = K^{-1} v for one wave (kinv_apply's two triangular mat-vecs without the split over
 // waves): lane i owns row i; v (in / out) and w are 64-float LDS vectors.  Four partial sums in a fixed
@@ -1158,34 +1203,173 @@ __device__ __forceinline__ void kinv_apply_wave(const float* __restrict__ z, flo
     __syncthreads();
 }
 
+// nc = 4 / 8: Z = L^{-1} by chol_inv_wave, the solves by kinv_apply_wave; workgroup barriers.
+template <int NC>
+struct FitSolverZ {   // float offsets of its scratch (every block a multiple of 4 floats)
+    static constexpr int W = NC, NI = (NC - 1) * (NC + 1);
+    static constexpr int L = 0, BV = L + ((NI * W + 3) & ~3), WV = BV + 64, Z = WV + 64,
+                         FLOATS = Z + ((NI * KINV_P + 3) & ~3);
+    static constexpr int STAGE = Z, STAGE_FLOATS = NI * KINV_P;   // free before the first factorisation
+    float* m;
+    __device__ __forceinline__ static void sync() { __syncthreads(); }
+    __device__ __forceinline__ float* b() const { return m + BV; }   // [64] right-hand side / solution
+    __device__ __forceinline__ void assemble(const float* kp, const float* Fs) const {
+        const int ii = threadIdx.x;
+        if (ii < NI) {
+            const BandRow row = band_row(NC, ii, Fs, LdsKappa{kp});
+            put_band_row(m + L + ii * W, W, row);
+            m[BV + ii] = row.rhs;
+        }
+    }
+    __device__ __forceinline__ void solve_primal() const {
+        chol_inv_wave<NC>(m + L, m + Z);
+        __syncthreads();
+        kinv_apply_wave<NC>(m + Z, m + BV, m + WV);
+    }
+    __device__ __forceinline__ void solve_adjoint() const { kinv_apply_wave<NC>(m + Z, m + BV, m + WV); }
+};
+// nc = 16: 255 unknowns have no Z = L^{-1} image: the three diagonals -> chol16_wave (forward substitution
+// riding along) -> back sweep; the adjoint by a forward sweep over Lc and a back sweep over Lr; wave_sync.
+struct FitSolver16 {
+    static constexpr int DG = 0, O1 = DG + 256, O15 = O1 + 256, B = O15 + 256, LR = B + 256, LC = LR + R16_LR,
+                         FLOATS = LC + R16_LC;
+    static constexpr int STAGE = LR, STAGE_FLOATS = R16_LR + R16_LC;
+    float* m;
+    __device__ __forceinline__ static void sync() { wave_sync(); }
+    __device__ __forceinline__ float* b() const { return m + B; }
+    __device__ __forceinline__ void assemble(const float* kp, const float* Fs) const {
+#pragma unroll
+        for (int ii = threadIdx.x; ii < R16_NI; ii += 64) {
+            const BandRow row = band_row(16, ii, Fs, LdsKappa{kp});
+            m[DG + ii] = row.dg;
+            m[O1 + ii] = row.o1;
+            m[O15 + ii] = row.on;
+            m[B + ii] = row.rhs;
+        }
+    }
+    __device__ __forceinline__ void solve_primal() const {
+        const Band16 A = {m + DG, m + O1, m + O15, 1};
+        chol16_wave(A, m + LR, m + LC, m + B);
+        band_sweep16<false>(m + LR, m + B);
+    }
+    __device__ __forceinline__ void solve_adjoint() const {
+        band_sweep16<true>(m + LC, m + B);
+        band_sweep16<false>(m + LR, m + B);
+    }
+};
+
 template <int NC>
 struct RomFitLds {   // float offsets after the fp64 block (every block a multiple of 4 floats)
-    static constexpr int NI = (NC - 1) * (NC + 1), NN = (NC + 1) * (NC + 1), NT2 = 2 * NC * NC;
-    static constexpr int NNP = (NN + 3) & ~3;
+    using Solver = std::conditional_t<NC == 16, FitSolver16, FitSolverZ<NC>>;
+    static constexpr int NN = (NC + 1) * (NC + 1), NT2 = 2 * NC * NC, NNP = (NN + 3) & ~3;
     static constexpr int ND = 5 * NN + (NN & 1);                 // doubles: G [4][NN], b [NN]
-    static constexpr int KP = 0, L = KP + NT2, U = L + ((NI * NC + 3) & ~3), LAM = U + NNP, FS = LAM + NNP,
-                         BV = FS + NNP, WV = BV + 64, Z = WV + 64, END = Z + ((NI * KINV_P + 3) & ~3);
+    static constexpr int KP = 0, U = KP + NT2, LAM = U + NNP, FS = LAM + NNP, SOLVER = FS + NNP,
+                         END = SOLVER + Solver::FLOATS;
     static constexpr size_t bytes = sizeof(double) * ND + sizeof(float) * END;
-    static_assert(sizeof(double) * 13 * NC * NC <= sizeof(float) * NI * KINV_P, "setup partials fit in Z");
+    static_assert(sizeof(double) * 13 * NC * NC <= sizeof(float) * Solver::STAGE_FLOATS, "setup partials fit in the factor");
+    static_assert((SOLVER + Solver::STAGE) % 2 == 0, "the fp64 staging area is 8-byte aligned");
+    static_assert(bytes <= 64 * 1024, "within the default dynamic-LDS limit");
 };
+
+// Setup, square q: the fp64 sums over its fine free nodes (Y: the sample's row) of W^T Y (4 corners), W^T W
+// (9 entries: 00 11 22 33 01 02 03 13 23) into sq[13], and of |Y|^2 onto cc.
+__device__ __forceinline__ void fit_square_sums(int nc, int r, int q, const float* Y, double& cc, double* sq) {
+    const int nf = nc * r;
+    const int I = q % nc, J = q / nc;
+    const int i0 = I == 0 ? 1 : I * r, i1 = (I + 1) * r - 1;     // free columns (inclusive)
+    const int rows = J == nc - 1 ? r + 1 : r;
+    const double rinv = 1.0 / (double)r;
+    double pb[4] = {0.0, 0.0, 0.0, 0.0};
+    double pg[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int jj = 0; jj < rows; ++jj) {
+        const float* yrow = Y + (int64_t)(J * r + jj) * (nf - 1) - 1;
+        const double eta = (double)jj * rinv;
+        for (int i = i0; i <= i1; ++i) {
+            const double y = (double)yrow[i];
+            const double xi = (double)(i - I * r) * rinv;
+            double w0, w1, w2, w3;                               // corners v0, +x, +y, +x+y
+            if (xi >= eta) { w0 = 1.0 - xi; w1 = xi - eta; w2 = 0.0; w3 = eta; }
+            else { w0 = 1.0 - eta; w1 = 0.0; w2 = eta - xi; w3 = xi; }
+            cc = fma(y, y, cc);
+            pb[0] = fma(w0, y, pb[0]); pb[1] = fma(w1, y, pb[1]);
+            pb[2] = fma(w2, y, pb[2]); pb[3] = fma(w3, y, pb[3]);
+            pg[0] = fma(w0, w0, pg[0]); pg[1] = fma(w1, w1, pg[1]);
+            pg[2] = fma(w2, w2, pg[2]); pg[3] = fma(w3, w3, pg[3]);
+            pg[4] = fma(w0, w1, pg[4]); pg[5] = fma(w0, w2, pg[5]); pg[6] = fma(w0, w3, pg[6]);
+            pg[7] = fma(w1, w3, pg[7]); pg[8] = fma(w2, w3, pg[8]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) sq[c] = pb[c];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) sq[4 + c] = pg[c];
+}
+// Setup, coarse node e: the shares of the (up to four) squares that hold it, in a fixed order, into
+// bn = W^T Y and the rows G [4][NN] = (p,p), (p,p+1), (p,p+nc+1), (p,p+nc+2) of W^T W.
+__device__ __forceinline__ void fit_node_gather(int nc, int e, const double* sq, double* bn, double* G) {
+    const int nn = (nc + 1) * (nc + 1);
+    const int I = e % (nc + 1), J = e / (nc + 1);
+    // the squares that hold node e, as their corner 3, 2, 1, 0
+    const int q3 = (I - 1) + nc * (J - 1), q2 = I + nc * (J - 1), q1 = (I - 1) + nc * J, q0 = I + nc * J;
+    const bool h3 = I > 0 && J > 0, h2 = I < nc && J > 0, h1 = I > 0 && J < nc, h0 = I < nc && J < nc;
+    double b = 0.0, gd = 0.0, gx = 0.0, gy = 0.0, gxy = 0.0;
+    if (h3) { b += sq[q3 * 13 + 3]; gd += sq[q3 * 13 + 4 + 3]; }
+    if (h2) { b += sq[q2 * 13 + 2]; gd += sq[q2 * 13 + 4 + 2]; gx += sq[q2 * 13 + 4 + 8]; }
+    if (h1) { b += sq[q1 * 13 + 1]; gd += sq[q1 * 13 + 4 + 1]; gy += sq[q1 * 13 + 4 + 7]; }
+    if (h0) {
+        b += sq[q0 * 13 + 0]; gd += sq[q0 * 13 + 4 + 0]; gx += sq[q0 * 13 + 4 + 4];
+        gy += sq[q0 * 13 + 4 + 5]; gxy = sq[q0 * 13 + 4 + 6];
+    }
+    bn[e] = b;
+    G[e] = gd; G[nn + e] = gx; G[2 * nn + e] = gy; G[3 * nn + e] = gxy;
+}
+// (G u)_e in fp64 (<= 7 non-zeros of the row)
+__device__ __forceinline__ double fit_gu_row(int nc, int e, const double* G, const float* u) {
+    const int nn = (nc + 1) * (nc + 1);
+    const int I = e % (nc + 1), J = e / (nc + 1);
+    double gu = G[e] * (double)u[e];
+    if (I > 0) gu = fma(G[nn + e - 1], (double)u[e - 1], gu);
+    if (I < nc) gu = fma(G[nn + e], (double)u[e + 1], gu);
+    if (J > 0) gu = fma(G[2 * nn + e - (nc + 1)], (double)u[e - (nc + 1)], gu);
+    if (J < nc) gu = fma(G[2 * nn + e], (double)u[e + (nc + 1)], gu);
+    if (I > 0 && J > 0) gu = fma(G[3 * nn + e - (nc + 2)], (double)u[e - (nc + 2)], gu);
+    if (I < nc && J < nc) gu = fma(G[3 * nn + e], (double)u[e + (nc + 2)], gu);
+    return gu;
+}
+// Adam's bias corrections of iteration `it` (torch.optim.Adam, step = step0 + it + 1)
+struct AdamStep {
+    float step_size, bc2_sqrt;
+};
+__device__ __forceinline__ AdamStep adam_step(const gpi_rom_fit_desc& d, int it) {
+    const int64_t step = d.step0 + it + 1;
+    const double bc1 = 1.0 - pow((double)d.beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)d.beta2, (double)step);
+    return {(float)((double)d.lr / bc1), (float)sqrt(bc2)};
+}
+// triangle t: dJ/dx by the edge formula, one Adam step on its x, m, v
+__device__ __forceinline__ void fit_update(const gpi_rom_fit_desc& d, const AdamStep& a, int nc, int t,
+                                           const float* lam, const float* u, const float* kp, float& x, float& m,
+                                           float& v) {
+    const float g = dx_of_dk(dk_edge(lam, u, nc, t), kp[t], false);
+    adam_element(g, x, m, v, d.beta1, d.beta2, d.eps, a.step_size, a.bc2_sqrt);
+}
 
 template <int NC>
 __global__ __launch_bounds__(64) void rom_fit_kernel(gpi_rom_fit_desc d, double gscale) {
     using S = RomFitLds<NC>;
-    constexpr int W = NC, BW = NC - 1, NI = S::NI, NN = S::NN, NT2 = S::NT2, NQ = NC * NC;
-    constexpr int KX = (NT2 + 63) / 64;                          // triangles per lane
+    using Solver = typename S::Solver;
+    constexpr int NN = S::NN, NT2 = S::NT2, NQ = NC * NC;
+    constexpr int KX = (NT2 + 63) / 64, KQ = (NQ + 63) / 64;     // triangles, squares per lane
     extern __shared__ __attribute__((aligned(16))) double smd[];
     double* G = smd;                   // [4][NN]: (p,p), (p,p+1), (p,p+nc+1), (p,p+nc+2)
     double* bn = G + 4 * NN;           // [NN] W^T Y
     float* sm = (float*)(smd + S::ND);
     float* kp = sm + S::KP;            // [NT2] kappa
-    float* L = sm + S::L;              // [NI * W] band rows
     float* u = sm + S::U;              // [NN] coarse solution
     float* lam = sm + S::LAM;          // [NN] adjoint (0 on the Dirichlet nodes)
     float* Fs = sm + S::FS;            // [NN] F_ROM_BC
-    float* bv = sm + S::BV;            // [64] right-hand side / solution of the interior system
-    float* wv = sm + S::WV;            // [64] kinv_apply_wave scratch
-    float* z = sm + S::Z;              // [NI][KINV_P] Z = L^{-1}; the setup's per-square sums before
+    const Solver slv = {sm + S::SOLVER};
+    float* bv = slv.b();               // right-hand side / solution of the interior system
     const int lane = threadIdx.x;
     const int64_t s = blockIdx.x;
     const int r = d.refine, nf = NC * r;
@@ -1195,58 +1379,15 @@ __global__ __launch_bounds__(64) void rom_fit_kernel(gpi_rom_fit_desc d, double 
     for (int e = lane; e < NN; e += 64) Fs[e] = d.F[s * NN + e];
     double cc = 0.0;
     {
-        double pb[4] = {0.0, 0.0, 0.0, 0.0};
-        double pg[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // 00 11 22 33 01 02 03 13 23
-        if (lane < NQ) {
-            const int I = lane % NC, J = lane / NC;
-            const int i0 = I == 0 ? 1 : I * r, i1 = (I + 1) * r - 1;     // free columns (inclusive)
-            const int rows = J == NC - 1 ? r + 1 : r;
-            const double rinv = 1.0 / (double)r;
-            for (int jj = 0; jj < rows; ++jj) {
-                const float* yrow = d.Y + s * dy + (int64_t)(J * r + jj) * (nf - 1) - 1;
-                const double eta = (double)jj * rinv;
-                for (int i = i0; i <= i1; ++i) {
-                    const double y = (double)yrow[i];
-                    const double xi = (double)(i - I * r) * rinv;
-                    double w0, w1, w2, w3;                               // corners v0, +x, +y, +x+y
-                    if (xi >= eta) { w0 = 1.0 - xi; w1 = xi - eta; w2 = 0.0; w3 = eta; }
-                    else { w0 = 1.0 - eta; w1 = 0.0; w2 = eta - xi; w3 = xi; }
-                    cc = fma(y, y, cc);
-                    pb[0] = fma(w0, y, pb[0]); pb[1] = fma(w1, y, pb[1]);
-                    pb[2] = fma(w2, y, pb[2]); pb[3] = fma(w3, y, pb[3]);
-                    pg[0] = fma(w0, w0, pg[0]); pg[1] = fma(w1, w1, pg[1]);
-                    pg[2] = fma(w2, w2, pg[2]); pg[3] = fma(w3, w3, pg[3]);
-                    pg[4] = fma(w0, w1, pg[4]); pg[5] = fma(w0, w2, pg[5]); pg[6] = fma(w0, w3, pg[6]);
-                    pg[7] = fma(w1, w3, pg[7]); pg[8] = fma(w2, w3, pg[8]);
-                }
-            }
-        }
-        double* sq = (double*)z;       // [NQ][13]
-        if (lane < NQ) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) sq[lane * 13 + c] = pb[c];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) sq[lane * 13 + 4 + c] = pg[c];
+        double* sq = (double*)(slv.m + Solver::STAGE);   // [NQ][13]
+        for (int k = 0; k < KQ; ++k) {
+            const int q = lane + 64 * k;
+            if (q < NQ) fit_square_sums(NC, r, q, d.Y + s * dy, cc, sq + q * 13);
         }
         cc = wave_sum_d(cc);
-        __syncthreads();
-        for (int e = lane; e < NN; e += 64) {
-            const int I = e % (NC + 1), J = e / (NC + 1);
-            // the squares that hold node e, as their corner 3, 2, 1, 0
-            const int q3 = (I - 1) + NC * (J - 1), q2 = I + NC * (J - 1), q1 = (I - 1) + NC * J, q0 = I + NC * J;
-            const bool h3 = I > 0 && J > 0, h2 = I < NC && J > 0, h1 = I > 0 && J < NC, h0 = I < NC && J < NC;
-            double b = 0.0, gd = 0.0, gx = 0.0, gy = 0.0, gxy = 0.0;
-            if (h3) { b += sq[q3 * 13 + 3]; gd += sq[q3 * 13 + 4 + 3]; }
-            if (h2) { b += sq[q2 * 13 + 2]; gd += sq[q2 * 13 + 4 + 2]; gx += sq[q2 * 13 + 4 + 8]; }
-            if (h1) { b += sq[q1 * 13 + 1]; gd += sq[q1 * 13 + 4 + 1]; gy += sq[q1 * 13 + 4 + 7]; }
-            if (h0) {
-                b += sq[q0 * 13 + 0]; gd += sq[q0 * 13 + 4 + 0]; gx += sq[q0 * 13 + 4 + 4];
-                gy += sq[q0 * 13 + 4 + 5]; gxy = sq[q0 * 13 + 4 + 6];
-            }
-            bn[e] = b;
-            G[e] = gd; G[NN + e] = gx; G[2 * NN + e] = gy; G[3 * NN + e] = gxy;
-        }
-        __syncthreads();               // z is free from here on
+        Solver::sync();
+        for (int e = lane; e < NN; e += 64) fit_node_gather(NC, e, sq, bn, G);
+        Solver::sync();                // the solver's storage is free from here on
     }
     if (lane == 0 && d.ynorm2) d.ynorm2[s] = cc;
     if (d.iters <= 0) return;
@@ -1267,88 +1408,44 @@ __global__ __launch_bounds__(64) void rom_fit_kernel(gpi_rom_fit_desc d, double 
         for (int k = 0; k < KX; ++k) {
             const int t = lane + 64 * k;
             if (t < NT2) {
-                const float kv = expf(xr[k]) + 1e-8f;
-                bad |= !(kv > 1e-12f);
-                kp[t] = kv;
+                kp[t] = kappa_of(xr[k], false, bad);
                 if (last && d.x_eval) d.x_eval[s * NT2 + t] = xr[k];
             }
         }
-        __syncthreads();
-        // ---- the interior system (banded lower) + rhs, as rom_kernel_fast
-        if (lane < NI) {
-            const int ii = lane;
-            const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
-            const int p = I + (NC + 1) * J;
-            const float chl = c_h(kp, NC, I - 1, J), chr = c_h(kp, NC, I, J);
-            const float cvd = J > 0 ? c_v(kp, NC, I, J - 1) : 0.f;
-            const float cvu = J < NC ? c_v(kp, NC, I, J) : 0.f;
-            float* row = L + ii * W;
-#pragma unroll
-            for (int t = 0; t < W; ++t) row[t] = 0.f;
-            row[0] = chl + chr + cvd + cvu;
-            if (I - 1 >= 1) row[1] += -chl;
-            if (J >= 1) row[BW] += -cvd;
-            float rhs = Fs[p];
-            if (I - 1 == 0) rhs += chl * Fs[p - 1];
-            if (I + 1 == NC) rhs += chr * Fs[p + 1];
-            bv[ii] = rhs;
-        }
-        __syncthreads();
-        chol_inv_wave<NC>(L, z);
-        __syncthreads();
-        kinv_apply_wave<NC>(z, bv, wv);
+        Solver::sync();
+        // ---- the interior system + rhs, the factorisation and u = K^{-1} rhs
+        slv.assemble(kp, Fs);
+        Solver::sync();
+        slv.solve_primal();
         for (int e = lane; e < NN; e += 64) {
-            const int I = e % (NC + 1), J = e / (NC + 1);
-            const float ue = (I == 0 || I == NC) ? Fs[e] : bv[J * (NC - 1) + (I - 1)];
+            const float ue = u_node(NC, e, Fs, bv);
             u[e] = ue;
             if (last && d.uc) d.uc[s * NN + e] = ue;
         }
-        __syncthreads();
+        Solver::sync();
         // ---- fp64: G u, the squared residual and its gradient
         double ssp = 0.0;
         for (int e = lane; e < NN; e += 64) {
             const int I = e % (NC + 1), J = e / (NC + 1);
-            double gu = G[e] * (double)u[e];
-            if (I > 0) gu = fma(G[NN + e - 1], (double)u[e - 1], gu);
-            if (I < NC) gu = fma(G[NN + e], (double)u[e + 1], gu);
-            if (J > 0) gu = fma(G[2 * NN + e - (NC + 1)], (double)u[e - (NC + 1)], gu);
-            if (J < NC) gu = fma(G[2 * NN + e], (double)u[e + (NC + 1)], gu);
-            if (I > 0 && J > 0) gu = fma(G[3 * NN + e - (NC + 2)], (double)u[e - (NC + 2)], gu);
-            if (I < NC && J < NC) gu = fma(G[3 * NN + e], (double)u[e + (NC + 2)], gu);
+            const double gu = fit_gu_row(NC, e, G, u);
             ssp = fma((double)u[e], gu - 2.0 * bn[e], ssp);
-            if (I > 0 && I < NC) bv[J * (NC - 1) + (I - 1)] = (float)(gscale * (gu - bn[e]));
+            if (I > 0 && I < NC) bv[interior_of(NC, I, J)] = (float)(gscale * (gu - bn[e]));
         }
         const double ss = wave_sum_d(ssp) + cc;
         bad |= !(fabs(ss) <= 1.7976931348623157e308);
         if (lane == 0 && d.sumsq) d.sumsq[(int64_t)it * d.n + s] = ss;
-        __syncthreads();
+        Solver::sync();
         // ---- adjoint lambda = K^{-1} g_u (interior), dJ/dx per coarse triangle, Adam
-        kinv_apply_wave<NC>(z, bv, wv);
-        for (int e = lane; e < NN; e += 64) {
-            const int I = e % (NC + 1), J = e / (NC + 1);
-            lam[e] = (I == 0 || I == NC) ? 0.f : bv[J * (NC - 1) + (I - 1)];
-        }
-        __syncthreads();
-        const int64_t step = d.step0 + it + 1;
-        const double bc1 = 1.0 - pow((double)d.beta1, (double)step);
-        const double bc2 = 1.0 - pow((double)d.beta2, (double)step);
-        const float step_size = (float)((double)d.lr / bc1);
-        const float bc2_sqrt = (float)sqrt(bc2);
+        slv.solve_adjoint();
+        for (int e = lane; e < NN; e += 64) lam[e] = lam_node(NC, e, bv);
+        Solver::sync();
+        const AdamStep as = adam_step(d, it);
 #pragma unroll
         for (int k = 0; k < KX; ++k) {
             const int t = lane + 64 * k;
-            if (t < NT2) {
-                const int q = t >> 1, ul = t & 1;
-                const int I = q % NC, J = q / NC;
-                const int v0 = I + (NC + 1) * J, v1 = v0 + 1, v2 = v0 + (NC + 1), v3 = v2 + 1;
-                float dk;
-                if (!ul) dk = -(lam[v0] - lam[v1]) * (u[v0] - u[v1]) - (lam[v1] - lam[v3]) * (u[v1] - u[v3]);
-                else dk = -(lam[v2] - lam[v3]) * (u[v2] - u[v3]) - (lam[v0] - lam[v2]) * (u[v0] - u[v2]);
-                const float g = 0.5f * dk * (kp[t] - 1e-8f);
-                adam_element(g, xr[k], mr[k], vr[k], d.beta1, d.beta2, d.eps, step_size, bc2_sqrt);
-            }
+            if (t < NT2) fit_update(d, as, NC, t, lam, u, kp, xr[k], mr[k], vr[k]);
         }
-        __syncthreads();               // kp, u, lam, bv are rewritten by the next iteration
+        Solver::sync();                // kp, u, lam, bv are rewritten by the next iteration
     }
 #pragma unroll
     for (int k = 0; k < KX; ++k) {
@@ -1362,207 +1459,9 @@ __global__ __launch_bounds__(64) void rom_fit_kernel(gpi_rom_fit_desc d, double 
     if (bad && d.flag) atomicOr(d.flag, 1);
 }
 
-// rom_fit16_kernel (gpi_rom_fit; nc = 16): the same fit on the 16 x 16 coarse mesh, ONE WAVE64 PER SAMPLE.
-// 256 squares and 512 triangles do not fit one per lane, and the 255-unknown system has no Z = L^{-1} image:
-//   setup      lane owns squares q = lane + 64 k (k = 0..3, in that order: c_n's partial is one chain per
-//              lane); the per-square sums are staged over Lr / Lc, which are free until the first iteration.
-//   iteration  kappa -> the three diagonals and the right-hand side of rom16_coarse_kernel -> chol16_wave
-//              (forward substitution riding along) -> back sweep = u -> the fp64 block of rom_fit_kernel
-//              -> forward sweep over Lc, back sweep over Lr = lambda -> edge formula, adam_element.
-// x, m, v: 8 triangles per lane in registers (t = lane + 64 k).  Every LDS hand-off between lanes is
-// followed by wave_sync() (the workgroup is one wave).
-struct RomFit16Lds {   // float offsets after the fp64 block (every block a multiple of 4 floats)
-    static constexpr int NN = 289, NNP = 292, NT2 = 512;
-    static constexpr int ND = 5 * NN + 1;                        // doubles: G [4][NN], b [NN]
-    static constexpr int KP = 0, DG = KP + NT2, O1 = DG + 256, O15 = O1 + 256, B = O15 + 256, U = B + 256,
-                         LAM = U + NNP, FS = LAM + NNP, LR = FS + NNP, LC = LR + R16_LR, END = LC + R16_LC;
-    static constexpr size_t bytes = sizeof(double) * ND + sizeof(float) * END;
-    static_assert(sizeof(double) * 13 * 256 <= sizeof(float) * (R16_LR + R16_LC), "setup partials fit in Lr / Lc");
-    static_assert(LR % 2 == 0, "the fp64 staging area over Lr is 8-byte aligned");
-    static_assert(bytes <= 64 * 1024, "within the default dynamic-LDS limit");
-};
-
-__global__ __launch_bounds__(64) void rom_fit16_kernel(gpi_rom_fit_desc d, double gscale) {
-    using S = RomFit16Lds;
-    constexpr int NC = 16, NN = S::NN, NT2 = S::NT2, NQ = NC * NC, KX = NT2 / 64, KQ = NQ / 64;
-    extern __shared__ __attribute__((aligned(16))) double smd[];
-    double* G = smd;                   // [4][NN]: (p,p), (p,p+1), (p,p+nc+1), (p,p+nc+2)
-    double* bn = G + 4 * NN;           // [NN] W^T Y
-    float* sm = (float*)(smd + S::ND);
-    float* kp = sm + S::KP;            // [NT2] kappa
-    float* dg = sm + S::DG;            // [256] each: diagonal, 1st / 15th sub-diagonal (Band16, stride 1)
-    float* o1 = sm + S::O1;
-    float* o15 = sm + S::O15;
-    float* b = sm + S::B;              // [256] right-hand side / solution of the interior system
-    float* u = sm + S::U;              // [NN] coarse solution
-    float* lam = sm + S::LAM;          // [NN] adjoint (0 on the Dirichlet nodes)
-    float* Fs = sm + S::FS;            // [NN] F_ROM_BC
-    float* Lr = sm + S::LR;            // [R16_LR]; with Lc the setup's per-square sums before
-    float* Lc = sm + S::LC;            // [R16_LC]
-    const int lane = threadIdx.x;
-    const int64_t s = blockIdx.x;
-    const int r = d.refine, nf = NC * r;
-    const int64_t dy = (int64_t)(nf + 1) * (nf - 1);
-
-    // ---- setup: b = W^T Y, c = |Y|^2, G = W^T W (fp64, fixed order)
-    for (int e = lane; e < NN; e += 64) Fs[e] = d.F[s * NN + e];
-    double cc = 0.0;
-    {
-        double* sq = (double*)Lr;      // [NQ][13]
-        const double rinv = 1.0 / (double)r;
-        for (int k = 0; k < KQ; ++k) {
-            const int q = lane + 64 * k;
-            double pb[4] = {0.0, 0.0, 0.0, 0.0};
-            double pg[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // 00 11 22 33 01 02 03 13 23
-            const int I = q % NC, J = q / NC;
-            const int i0 = I == 0 ? 1 : I * r, i1 = (I + 1) * r - 1;     // free columns (inclusive)
-            const int rows = J == NC - 1 ? r + 1 : r;
-            for (int jj = 0; jj < rows; ++jj) {
-                const float* yrow = d.Y + s * dy + (int64_t)(J * r + jj) * (nf - 1) - 1;
-                const double eta = (double)jj * rinv;
-                for (int i = i0; i <= i1; ++i) {
-                    const double y = (double)yrow[i];
-                    const double xi = (double)(i - I * r) * rinv;
-                    double w0, w1, w2, w3;                               // corners v0, +x, +y, +x+y
-                    if (xi >= eta) { w0 = 1.0 - xi; w1 = xi - eta; w2 = 0.0; w3 = eta; }
-                    else { w0 = 1.0 - eta; w1 = 0.0; w2 = eta - xi; w3 = xi; }
-                    cc = fma(y, y, cc);
-                    pb[0] = fma(w0, y, pb[0]); pb[1] = fma(w1, y, pb[1]);
-                    pb[2] = fma(w2, y, pb[2]); pb[3] = fma(w3, y, pb[3]);
-                    pg[0] = fma(w0, w0, pg[0]); pg[1] = fma(w1, w1, pg[1]);
-                    pg[2] = fma(w2, w2, pg[2]); pg[3] = fma(w3, w3, pg[3]);
-                    pg[4] = fma(w0, w1, pg[4]); pg[5] = fma(w0, w2, pg[5]); pg[6] = fma(w0, w3, pg[6]);
-                    pg[7] = fma(w1, w3, pg[7]); pg[8] = fma(w2, w3, pg[8]);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) sq[q * 13 + c] = pb[c];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) sq[q * 13 + 4 + c] = pg[c];
-        }
-        cc = wave_sum_d(cc);
-        wave_sync();
-        for (int e = lane; e < NN; e += 64) {
-            const int I = e % (NC + 1), J = e / (NC + 1);
-            // the squares that hold node e, as their corner 3, 2, 1, 0
-            const int q3 = (I - 1) + NC * (J - 1), q2 = I + NC * (J - 1), q1 = (I - 1) + NC * J, q0 = I + NC * J;
-            const bool h3 = I > 0 && J > 0, h2 = I < NC && J > 0, h1 = I > 0 && J < NC, h0 = I < NC && J < NC;
-            double bb = 0.0, gd = 0.0, gx = 0.0, gy = 0.0, gxy = 0.0;
-            if (h3) { bb += sq[q3 * 13 + 3]; gd += sq[q3 * 13 + 4 + 3]; }
-            if (h2) { bb += sq[q2 * 13 + 2]; gd += sq[q2 * 13 + 4 + 2]; gx += sq[q2 * 13 + 4 + 8]; }
-            if (h1) { bb += sq[q1 * 13 + 1]; gd += sq[q1 * 13 + 4 + 1]; gy += sq[q1 * 13 + 4 + 7]; }
-            if (h0) {
-                bb += sq[q0 * 13 + 0]; gd += sq[q0 * 13 + 4 + 0]; gx += sq[q0 * 13 + 4 + 4];
-                gy += sq[q0 * 13 + 4 + 5]; gxy = sq[q0 * 13 + 4 + 6];
-            }
-            bn[e] = bb;
-            G[e] = gd; G[NN + e] = gx; G[2 * NN + e] = gy; G[3 * NN + e] = gxy;
-        }
-        wave_sync();                   // Lr / Lc are free from here on
-    }
-    if (lane == 0 && d.ynorm2) d.ynorm2[s] = cc;
-    if (d.iters <= 0) return;
-
-    float xr[KX], mr[KX], vr[KX];
-#pragma unroll
-    for (int k = 0; k < KX; ++k) {
-        const int t = lane + 64 * k;
-        xr[k] = d.x[s * d.x_stride + t];
-        mr[k] = d.m ? d.m[s * NT2 + t] : 0.f;
-        vr[k] = d.v ? d.v[s * NT2 + t] : 0.f;
-    }
-    bool bad = false;
-    const Band16 A = {dg, o1, o15, 1};
-    for (int it = 0; it < d.iters; ++it) {
-        const bool last = it == d.iters - 1;
-#pragma unroll
-        for (int k = 0; k < KX; ++k) {
-            const int t = lane + 64 * k;
-            const float kv = expf(xr[k]) + 1e-8f;
-            bad |= !(kv > 1e-12f);
-            kp[t] = kv;
-            if (last && d.x_eval) d.x_eval[s * NT2 + t] = xr[k];
-        }
-        wave_sync();
-        // ---- the interior system as three diagonals + rhs, as rom16_coarse_kernel
-#pragma unroll
-        for (int ii = lane; ii < R16_NI; ii += 64) {
-            const int J = ii / (NC - 1), I = ii - J * (NC - 1) + 1;
-            const int p = I + (NC + 1) * J;
-            const float chl = c_h(kp, NC, I - 1, J), chr = c_h(kp, NC, I, J);
-            const float cvd = J > 0 ? c_v(kp, NC, I, J - 1) : 0.f;
-            const float cvu = J < NC ? c_v(kp, NC, I, J) : 0.f;
-            dg[ii] = chl + chr + cvd + cvu;
-            o1[ii] = I - 1 >= 1 ? -chl : 0.f;
-            o15[ii] = J >= 1 ? -cvd : 0.f;
-            float rhs = Fs[p];
-            if (I - 1 == 0) rhs += chl * Fs[p - 1];
-            if (I + 1 == NC) rhs += chr * Fs[p + 1];
-            b[ii] = rhs;
-        }
-        wave_sync();
-        chol16_wave(A, Lr, Lc, b);
-        band_sweep16<false>(Lr, b);
-        for (int e = lane; e < NN; e += 64) {
-            const int I = e % (NC + 1), J = e / (NC + 1);
-            const float ue = (I == 0 || I == NC) ? Fs[e] : b[J * (NC - 1) + (I - 1)];
-            u[e] = ue;
-            if (last && d.uc) d.uc[s * NN + e] = ue;
-        }
-        wave_sync();
-        // ---- fp64: G u, the squared residual and its gradient
-        double ssp = 0.0;
-        for (int e = lane; e < NN; e += 64) {
-            const int I = e % (NC + 1), J = e / (NC + 1);
-            double gu = G[e] * (double)u[e];
-            if (I > 0) gu = fma(G[NN + e - 1], (double)u[e - 1], gu);
-            if (I < NC) gu = fma(G[NN + e], (double)u[e + 1], gu);
-            if (J > 0) gu = fma(G[2 * NN + e - (NC + 1)], (double)u[e - (NC + 1)], gu);
-            if (J < NC) gu = fma(G[2 * NN + e], (double)u[e + (NC + 1)], gu);
-            if (I > 0 && J > 0) gu = fma(G[3 * NN + e - (NC + 2)], (double)u[e - (NC + 2)], gu);
-            if (I < NC && J < NC) gu = fma(G[3 * NN + e], (double)u[e + (NC + 2)], gu);
-            ssp = fma((double)u[e], gu - 2.0 * bn[e], ssp);
-            if (I > 0 && I < NC) b[J * (NC - 1) + (I - 1)] = (float)(gscale * (gu - bn[e]));
-        }
-        const double ss = wave_sum_d(ssp) + cc;
-        bad |= !(fabs(ss) <= 1.7976931348623157e308);
-        if (lane == 0 && d.sumsq) d.sumsq[(int64_t)it * d.n + s] = ss;
-        wave_sync();
-        // ---- adjoint lambda = K^{-1} g_u (interior), dJ/dx per coarse triangle, Adam
-        band_sweep16<true>(Lc, b);
-        band_sweep16<false>(Lr, b);
-        for (int e = lane; e < NN; e += 64) {
-            const int I = e % (NC + 1), J = e / (NC + 1);
-            lam[e] = (I == 0 || I == NC) ? 0.f : b[J * (NC - 1) + (I - 1)];
-        }
-        wave_sync();
-        const int64_t step = d.step0 + it + 1;
-        const double bc1 = 1.0 - pow((double)d.beta1, (double)step);
-        const double bc2 = 1.0 - pow((double)d.beta2, (double)step);
-        const float step_size = (float)((double)d.lr / bc1);
-        const float bc2_sqrt = (float)sqrt(bc2);
-#pragma unroll
-        for (int k = 0; k < KX; ++k) {
-            const int t = lane + 64 * k;
-            const int q = t >> 1, ul = t & 1;
-            const int I = q % NC, J = q / NC;
-            const int v0 = I + (NC + 1) * J, v1 = v0 + 1, v2 = v0 + (NC + 1), v3 = v2 + 1;
-            float dk;
-            if (!ul) dk = -(lam[v0] - lam[v1]) * (u[v0] - u[v1]) - (lam[v1] - lam[v3]) * (u[v1] - u[v3]);
-            else dk = -(lam[v2] - lam[v3]) * (u[v2] - u[v3]) - (lam[v0] - lam[v2]) * (u[v0] - u[v2]);
-            const float g = 0.5f * dk * (kp[t] - 1e-8f);
-            adam_element(g, xr[k], mr[k], vr[k], d.beta1, d.beta2, d.eps, step_size, bc2_sqrt);
-        }
-        wave_sync();                   // kp, u, lam, b are rewritten by the next iteration
-    }
-#pragma unroll
-    for (int k = 0; k < KX; ++k) {
-        const int t = lane + 64 * k;
-        d.x[s * d.x_stride + t] = xr[k];
-        if (d.m) d.m[s * NT2 + t] = mr[k];
-        if (d.v) d.v[s * NT2 + t] = vr[k];
-    }
-    if (bad && d.flag) atomicOr(d.flag, 1);
+template <int NC, int NT>
+void launch_fast(const gpi_rom_desc* d, const RomDims& D, void* stream) {
+    hipLaunchKernelGGL((rom_kernel_fast<NC, NT>), dim3(d->n), dim3(NT), (RomFastLds<NC, NT>::bytes), (hipStream_t)stream, *d, D);
 }
 
 }  // namespace
@@ -1586,7 +1485,7 @@ extern "C" int gpi_rom_fit(const gpi_rom_fit_desc* d, void* stream) {
     // d/du of the MSE mean: 2 / (n_total d_y) (G u - b)
     const double gscale = 2.0 / ((double)(d->n_total ? d->n_total : d->n) * (double)dy);
     if (d->nc == 16)
-        hipLaunchKernelGGL(rom_fit16_kernel, dim3(d->n), dim3(64), RomFit16Lds::bytes, (hipStream_t)stream, *d, gscale);
+        hipLaunchKernelGGL(rom_fit_kernel<16>, dim3(d->n), dim3(64), RomFitLds<16>::bytes, (hipStream_t)stream, *d, gscale);
     else if (d->nc == 8)
         hipLaunchKernelGGL(rom_fit_kernel<8>, dim3(d->n), dim3(64), RomFitLds<8>::bytes, (hipStream_t)stream, *d, gscale);
     else
@@ -1611,7 +1510,7 @@ extern "C" int gpi_rom(const gpi_rom_desc* d, void* stream) {
     D.n = d->nc * d->refine;
     D.dy = (D.n + 1) * (D.n - 1);
     if (d->mode == GPI_ROM_FORWARD && !d->mu_y && d->uc && (d->nc == 4 || d->nc == 8)) {
-        const size_t lds = sizeof(float) * 64 * (D.nI * (D.bw + 1) + D.nI);
+        const size_t lds = d->nc == 8 ? RomLaneLds<8>::bytes : RomLaneLds<4>::bytes;
         const void* k = d->nc == 8 ? (const void*)rom_lane_kernel<8> : (const void*)rom_lane_kernel<4>;
         if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return GPI_ERR_LAUNCH;
@@ -1625,11 +1524,9 @@ extern "C" int gpi_rom(const gpi_rom_desc* d, void* stream) {
     if (d->nc == 16 && !slow) {
         if (d->mode == GPI_ROM_FORWARD && !d->mu_y && d->uc) {
             const dim3 grid((d->n + R16C_SPW - 1) / R16C_SPW);
-            hipLaunchKernelGGL(rom16_coarse_kernel, grid, dim3(64 * R16C_SPW), sizeof(float) * R16C_SPW * R16C_FLOATS,
-                               (hipStream_t)stream, *d);
+            hipLaunchKernelGGL(rom16_coarse_kernel, grid, dim3(64 * R16C_SPW), Rom16CoarseLds::bytes, (hipStream_t)stream, *d);
         } else {
-            const size_t lds_16 = rom_fast_lds<16, 512>();
-            hipLaunchKernelGGL((rom_kernel_fast<16, 512>), dim3(d->n), dim3(512), lds_16, (hipStream_t)stream, *d, D);
+            launch_fast<16, 512>(d, D, stream);
         }
         GPI_CHECK_LAUNCH();
         return GPI_OK;
@@ -1637,21 +1534,14 @@ extern "C" int gpi_rom(const gpi_rom_desc* d, void* stream) {
     if ((d->nc == 8 || d->nc == 4) && !slow) {
         // nc = 8: the workgroup width (GPI_ROM_FAST_NT = 256 / 512 / 1024; r03 A/B in DESIGN.md)
         static const int fnt = getenv("GPI_ROM_FAST_NT") ? atoi(getenv("GPI_ROM_FAST_NT")) : GPI_ROM_FAST_NT_DEFAULT;
-        const size_t lds_8_1024 = rom_fast_lds<8, 1024>(), lds_8_512 = rom_fast_lds<8, 512>();
-        const size_t lds_8_256 = rom_fast_lds<8, 256>(), lds_4_256 = rom_fast_lds<4, 256>();
-        if (d->nc == 8 && fnt == 1024)
-            hipLaunchKernelGGL((rom_kernel_fast<8, 1024>), dim3(d->n), dim3(1024), lds_8_1024, (hipStream_t)stream, *d, D);
-        else if (d->nc == 8 && fnt == 512)
-            hipLaunchKernelGGL((rom_kernel_fast<8, 512>), dim3(d->n), dim3(512), lds_8_512, (hipStream_t)stream, *d, D);
-        else if (d->nc == 8)
-            hipLaunchKernelGGL((rom_kernel_fast<8, 256>), dim3(d->n), dim3(256), lds_8_256, (hipStream_t)stream, *d, D);
-        else
-            hipLaunchKernelGGL((rom_kernel_fast<4, 256>), dim3(d->n), dim3(256), lds_4_256, (hipStream_t)stream, *d, D);
+        if (d->nc == 8 && fnt == 1024) launch_fast<8, 1024>(d, D, stream);
+        else if (d->nc == 8 && fnt == 512) launch_fast<8, 512>(d, D, stream);
+        else if (d->nc == 8) launch_fast<8, 256>(d, D, stream);
+        else launch_fast<4, 256>(d, D, stream);
         GPI_CHECK_LAUNCH();
         return GPI_OK;
     }
-    const size_t lds = sizeof(float) * (D.nT + D.nI * (D.bw + 1) + 4 * D.nn + 2 * D.nI + 2 * (ROM_NT / 64) + 4);
-    hipLaunchKernelGGL(rom_kernel, dim3(d->n), dim3(ROM_NT), lds, (hipStream_t)stream, *d, D);
+    hipLaunchKernelGGL(rom_kernel, dim3(d->n), dim3(ROM_NT), rom_lds(D).bytes, (hipStream_t)stream, *d, D);
     GPI_CHECK_LAUNCH();
     return GPI_OK;
 }

@@ -6,7 +6,7 @@ J = MSELoss(forward_mean(x, F), Y) over x, one wave per sample, the fine grid re
 (|W u - Y|^2 = u^T G u - 2 b^T u + c with G = W^T W, b = W^T Y, c = |Y|^2 in fp64).  No host
 synchronisation here; the records stay on the device until the caller reads them.
 
-Coarse meshes: nc = 4, 8 (rom_fit_kernel) and 16 (rom_fit16_kernel: the band factor and three sweeps per
+Coarse meshes: nc = 4, 8 and 16 (rom_fit_kernel<NC>; nc = 16: the band factor and three sweeps per
 iteration).  Any other nc raises NativeError (GPI_ERR_UNSUPPORTED); nothing falls back to a host loop here.
 """
 import ctypes as C

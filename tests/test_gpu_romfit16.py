@@ -1,4 +1,4 @@
-"""gpi_rom_fit at nc = 16 (rom_fit16_kernel) and OptimizeEffectiveProperties on the 16 x 16 coarse mesh.
+"""gpi_rom_fit at nc = 16 (rom_fit_kernel<16>) and OptimizeEffectiveProperties on the 16 x 16 coarse mesh.
 
 The checks of tests/test_gpu_romfit.py on the smallest shapes at which the nc = 16 kernel can go wrong:
 r = 1 (d_y = 255: every fine node is a coarse node, the i0 / rows edge cases of the setup), r = 2

@@ -14,7 +14,7 @@ import torch
 
 import lamp.modules
 from bottleneck.components import VariationalApproximation
-from bottleneck.utils import DiagonalGaussianLogLikelihood
+from bottleneck.utils import DiagonalGaussianLogLikelihood, ObservedDofs
 from gpi.engine import ElboEngine
 from gpi.flat import FlatParameters
 from gpi.native import anchor, set_flat, engine_for
@@ -67,8 +67,57 @@ class GenerativeModel(lamp.modules.BaseModule):
         self._independent_X = gp.independent_X
         self.config = {'reconstruct_log_eff_property': True}
         self._tensorboard_logging_interval = 1
-        self.preprocess_y_fct = None
+        self._preprocess_y_fct = None
+        self._label_mask = None
         self._flat = None
+
+    # ------------------------------------------------------------ partially observed labels
+    @property
+    def preprocess_y_fct(self):
+        """The reference's label hook (generative.py:49-56), applied to Y, mu_y and logsigmas_y in the
+        labelled likelihood.  The native path takes a bottleneck.utils.ObservedDofs (labels known at sensor
+        nodes: a 0/1 observation weight per entry in the ROM launch); any other callable raises
+        NotImplementedError when the labelled term is evaluated."""
+        return self._preprocess_y_fct
+
+    @preprocess_y_fct.setter
+    def preprocess_y_fct(self, fct):
+        if fct is not None and self._label_mask is not None:
+            raise ValueError('preprocess_y_fct and set_label_mask exclude each other: clear the mask first')
+        self._preprocess_y_fct = fct
+
+    def set_label_mask(self, mask):
+        """Per-sample sensors: mask [N_s, d_y] (bool or float 0/1, on the device) marks the observed entries
+        of the registered supervised labels; None clears it.  Unobserved entries of Y are never read into
+        the result (they may hold NaN).  A contiguous fp32 mask is kept as it is, so an in-place edit is
+        seen by the next elbo() / step; any other is converted once."""
+        if mask is None:
+            self._label_mask = None
+            return
+        if self._preprocess_y_fct is not None:
+            raise ValueError('preprocess_y_fct and set_label_mask exclude each other: clear preprocess_y_fct first')
+        ds = self._datasets.get('supervised')
+        if not ds:
+            raise ValueError('set_label_mask: register the supervised data first')
+        shape = tuple(ds.get('Y').shape)
+        if tuple(mask.shape) != shape:
+            raise ValueError('set_label_mask: mask %s does not match the supervised labels %s'
+                             % (tuple(mask.shape), shape))
+        L.require_device(mask)
+        self._label_mask = mask.to(torch.float32).contiguous()
+
+    def label_weights(self, N_s=None):
+        """The labelled term's observation weights for the ROM launch: None (every entry observed), the
+        shared fp32 row [d_y] of an ObservedDofs, or the per-sample mask [N_s, d_y]."""
+        fct = self._preprocess_y_fct
+        if fct is not None:
+            if not isinstance(fct, ObservedDofs):
+                raise NotImplementedError('preprocess_y_fct is not supported on the native path')
+            return fct.weights(self.dim_y, next(self.parameters()).device)
+        m = self._label_mask
+        if m is not None and N_s is not None and m.shape[0] != N_s:
+            raise ValueError('the label mask has %d rows, the labelled batch %d' % (m.shape[0], N_s))
+        return m
 
     # ------------------------------------------------------------ plumbing
     def set(self, ckey, value):
@@ -180,10 +229,15 @@ class GenerativeModel(lamp.modules.BaseModule):
 
     def _elbo_engine(self, B_u, N_s, normalize, N_vo=0, vo_holdoff=False, q_unsup=None):
         flat = self.native_flat()
-        return engine_for(self, ('elbo', B_u, N_s, N_vo, bool(vo_holdoff), bool(normalize), id(flat),
-                                 q_unsup is not None, bool(self.config['reconstruct_log_eff_property'])),
+        key = ('elbo', B_u, N_s, N_vo, bool(vo_holdoff), bool(normalize), id(flat),
+               q_unsup is not None, bool(self.config['reconstruct_log_eff_property']))
+        yw = self.label_weights(N_s) if N_s > 0 else None
+        if yw is not None:
+            # (an engine per mask tensor; the engine keeps the tensor, so its address stays this mask's)
+            key = key + (yw.data_ptr(), tuple(yw.shape))
+        return engine_for(self, key,
                           lambda: ElboEngine(self, B_u, N_s, normalize=normalize, N_vo=N_vo, vo_holdoff=vo_holdoff,
-                                             q_unsup=q_unsup))
+                                             q_unsup=q_unsup, y_weight=yw))
 
     @staticmethod
     def _host_seed():
@@ -318,9 +372,8 @@ class GenerativeModel(lamp.modules.BaseModule):
         if self._datasets.get('supervised') and not self.disable_elbo_supervised:
             ds = self._datasets['supervised']
             X_s, Y, F = ds.get('X').detach(), ds.get('Y').detach(), ds.get('F_ROM_BC').detach()
-            if self.preprocess_y_fct is not None:
-                raise NotImplementedError('preprocess_y_fct is not supported on the native path')
             N_s = X_s.shape[0]
+            self.label_weights(N_s)         # (raises for a preprocess_y_fct the native path does not take)
         if B_u == 0 and N_s == 0 and N_vo == 0:
             return 0
         engine = self._elbo_engine(B_u, N_s, normalize, N_vo=N_vo, vo_holdoff=vo_holdoff, q_unsup=q_unsup)

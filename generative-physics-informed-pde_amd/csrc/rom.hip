@@ -14,7 +14,9 @@
 //   * LOGLIK mode fuses DiagonalGaussianLogLikelihood(Y, mu_y, 2 logsigma_y)
 //     and its adjoint: lambda = K_II^{-1} W^T dmu,
 //     dJ/dc_pq = -(lambda_p - lambda_q)(u_p - u_q), dJ/dkappa_t = 1/2 sum over
-//     its two legs, dJ/dx = dJ/dkappa * exp(x);
+//     its two legs, dJ/dx = dJ/dkappa * exp(x); optional 0/1 observation weights of the label entries (y_weight:
+//     partially observed labels; an entry with weight 0 is never read into a result), as instantiations of their
+//     own (YW), so that a launch without weights runs the kernels it ran before;
 //   * nc = 4 / 8: rom_kernel_fast (Z = L^{-1} by one wave) and rom_lane_kernel; nc = 16: rom_kernel_fast<16> with
 //     the factorisation and the band sweeps by one wave whose lanes share the window (chol16_wave, band_sweep16)
 //     and rom16_coarse_kernel; any other nc <= 16, and GPI_ROM_SLOW=1: the barrier-per-step rom_kernel;
@@ -328,6 +330,12 @@ constexpr int ROM_U = 8;         // fine nodes per batch of global loads
 #define GPI_ROM_FAST_NT_DEFAULT 512
 #endif
 
+// observation weight of label entry (row s, fine free node pp) of a launch that has weights (d.y_weight:
+// one shared row at yw_stride = 0, or rows [n, d_y])
+__device__ __forceinline__ float rom_yw(const gpi_rom_desc& d, int64_t s, int pp) {
+    return d.y_weight[s * d.yw_stride + pp];
+}
+
 // the workgroup's log-likelihood: per-wave sums through lred[NW], in wave order, into the sample's replica
 template <int NW>
 __device__ __forceinline__ void loglik_sum(const gpi_rom_desc& d, float Lsum, double* lred) {
@@ -373,6 +381,9 @@ __host__ __device__ __forceinline__ RomLds rom_lds(const RomDims& D) {
     return o;
 }
 
+// YW: the launch has observation weights (d.y_weight).  The weighted form is its own instantiation, so a
+// launch without weights runs the code it ran before there were any.
+template <bool YW>
 __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const RomLds o = rom_lds(D);
@@ -439,7 +450,7 @@ __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) 
             const int ncol = i1 - i0 + 1, total = rows * ncol;
             for (int e0 = sub; e0 < total; e0 += 4 * ROM_U) {
                 int pp[ROM_U];
-                float yv[ROM_U], lv[ROM_U], gv[ROM_U];
+                float yv[ROM_U], lv[ROM_U], gv[ROM_U], wv[YW ? ROM_U : 1];
 #pragma unroll
                 for (int k = 0; k < ROM_U; ++k) {
                     const int e = min(e0 + 4 * k, total - 1);
@@ -451,6 +462,7 @@ __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) 
                     for (int k = 0; k < ROM_U; ++k) {
                         yv[k] = d.Y[(int64_t)s * D.dy + pp[k]];
                         lv[k] = d.logsig_y[pp[k]];
+                        if constexpr (YW) wv[k] = rom_yw(d, s, pp[k]);
                     }
                 } else if (want_g) {
 #pragma unroll
@@ -472,11 +484,27 @@ __global__ __launch_bounds__(ROM_NT) void rom_kernel(gpi_rom_desc d, RomDims D) 
                     if (d.mode == GPI_ROM_LOGLIK) {
                         const float ee = expf(-2.f * lv[k]);
                         const float rr = yv[k] - mu;
-                        Lsum += -0.5f * (2.f * lv[k] + rr * rr * ee + GPI_LOG2PI);
-                        g = -d.loss_scale * rr * ee;
-                        const float gl = d.loss_scale * (1.f - rr * rr * ee);
-                        if (d.gls_part) d.gls_part[(int64_t)s * D.dy + pp[k]] = gl;
-                        else atomicAdd(d.gacc_logsig + pp[k], (double)gl);
+                        if constexpr (YW) {
+                            // an unobserved entry contributes exactly 0, whatever Y holds there (a select: 0 * NaN
+                            // would not do); w = 1 leaves every value as the unweighted form computes it.  That form
+                            // rounds every product on its own (rr^2 ee feeds two sums, so it is never fused into
+                            // either); written here with contraction off, or the compiler fuses these into other bits
+#pragma clang fp contract(off)
+                            const bool obs = wv[k] != 0.f;
+                            const float r2e = rr * rr * ee;
+                            const float ll = -0.5f * (2.f * lv[k] + r2e + GPI_LOG2PI);
+                            Lsum += obs ? wv[k] * ll : 0.f;
+                            g = obs ? wv[k] * (-d.loss_scale * rr * ee) : 0.f;
+                            const float gl = obs ? wv[k] * (d.loss_scale * (1.f - r2e)) : 0.f;
+                            if (d.gls_part) d.gls_part[(int64_t)s * D.dy + pp[k]] = gl;
+                            else if (obs) atomicAdd(d.gacc_logsig + pp[k], (double)gl);
+                        } else {
+                            Lsum += -0.5f * (2.f * lv[k] + rr * rr * ee + GPI_LOG2PI);
+                            g = -d.loss_scale * rr * ee;
+                            const float gl = d.loss_scale * (1.f - rr * rr * ee);
+                            if (d.gls_part) d.gls_part[(int64_t)s * D.dy + pp[k]] = gl;
+                            else atomicAdd(d.gacc_logsig + pp[k], (double)gl);
+                        }
                     } else {
                         g = gv[k];
                     }
@@ -780,7 +808,8 @@ struct RomFastLds {   // float offsets; the fp64 block (du [NN], lred [NW]) at t
     static constexpr size_t bytes = sizeof(float) * DU + sizeof(double) * (NN + NW);
 };
 
-template <int NC, int NT>
+// YW: the launch has observation weights; they join the prefetched Y / logsigma_y operands (rom_kernel's note).
+template <int NC, int NT, bool YW>
 __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D) {
     using S = RomFastLds<NC, NT>;
     constexpr int NI = S::NI, NN = S::NN, NT2 = S::NT2, SUB = NT / 64, NW = S::NW;
@@ -803,7 +832,7 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
 
     // ---- entry: every global read in flight (kappa, F, and this thread's first PF fine nodes)
     const int q0 = tid / SUB, sub = tid & (SUB - 1);
-    float ypf[PF], lpf[PF];
+    float ypf[PF], lpf[PF], wpf[YW ? PF : 1];
     {
         const bool okq = q0 < NC * NC && d.mode == GPI_ROM_LOGLIK;
         const int I = q0 % NC, J = q0 / NC;
@@ -819,6 +848,7 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
             const int pp = (J * r + jj) * (nf - 1) + (i0 + ii - 1);
             ypf[k] = ok ? d.Y[(int64_t)s * D.dy + pp] : 0.f;
             lpf[k] = ok ? d.logsig_y[pp] : 0.f;
+            if constexpr (YW) wpf[k] = ok ? rom_yw(d, s, pp) : 0.f;
         }
     }
     bool bad = false;
@@ -841,6 +871,10 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
     // kappa and F): otherwise the compiler sinks the loads to the prolongation, a round trip there
 #pragma unroll
     for (int k = 0; k < PF; ++k) asm volatile("" : : "v"(ypf[k]), "v"(lpf[k]));
+    if constexpr (YW) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) asm volatile("" : : "v"(wpf[k]));
+    }
     if constexpr (NC == 16) {
         // wave 0: band factorisation with the forward substitution of b riding along, then the back sweep
         if (tid < 64) {
@@ -886,7 +920,7 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
                 const int bi = (e0 - sub) / (SUB * ROM_U);
                 const bool pre = qb == 0 && bi < PF / ROM_U;
                 int pp[ROM_U];
-                float yv[ROM_U], lv[ROM_U], gv[ROM_U];
+                float yv[ROM_U], lv[ROM_U], gv[ROM_U], wv[YW ? ROM_U : 1];
 #pragma unroll
                 for (int k = 0; k < ROM_U; ++k) {
                     const int e = min(e0 + SUB * k, total - 1);
@@ -900,9 +934,11 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
                             if constexpr (PF == ROM_U) {
                                 yv[k] = ypf[k];
                                 lv[k] = lpf[k];
+                                if constexpr (YW) wv[k] = wpf[k];
                             } else {
                                 yv[k] = bi == 0 ? ypf[k] : (bi == 1 ? ypf[ROM_U + k] : ypf[2 * ROM_U + k]);
                                 lv[k] = bi == 0 ? lpf[k] : (bi == 1 ? lpf[ROM_U + k] : lpf[2 * ROM_U + k]);
+                                if constexpr (YW) wv[k] = bi == 0 ? wpf[k] : (bi == 1 ? wpf[ROM_U + k] : wpf[2 * ROM_U + k]);
                             }
                         }
                     } else {
@@ -910,6 +946,7 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
                         for (int k = 0; k < ROM_U; ++k) {
                             yv[k] = d.Y[(int64_t)s * D.dy + pp[k]];
                             lv[k] = d.logsig_y[pp[k]];
+                            if constexpr (YW) wv[k] = rom_yw(d, s, pp[k]);
                         }
                     }
                 } else if (want_g) {
@@ -932,11 +969,27 @@ __global__ __launch_bounds__(NT) void rom_kernel_fast(gpi_rom_desc d, RomDims D)
                     if (d.mode == GPI_ROM_LOGLIK) {
                         const float ee = expf(-2.f * lv[k]);
                         const float rr = yv[k] - mu;
-                        Lsum += -0.5f * (2.f * lv[k] + rr * rr * ee + GPI_LOG2PI);
-                        g = -d.loss_scale * rr * ee;
-                        const float gl = d.loss_scale * (1.f - rr * rr * ee);
-                        if (d.gls_part) d.gls_part[(int64_t)s * D.dy + pp[k]] = gl;
-                        else atomicAdd(d.gacc_logsig + pp[k], (double)gl);
+                        if constexpr (YW) {
+                            // an unobserved entry contributes exactly 0, whatever Y holds there (a select: 0 * NaN
+                            // would not do); w = 1 leaves every value as the unweighted form computes it.  That form
+                            // rounds every product on its own (rr^2 ee feeds two sums, so it is never fused into
+                            // either); written here with contraction off, or the compiler fuses these into other bits
+#pragma clang fp contract(off)
+                            const bool obs = wv[k] != 0.f;
+                            const float r2e = rr * rr * ee;
+                            const float ll = -0.5f * (2.f * lv[k] + r2e + GPI_LOG2PI);
+                            Lsum += obs ? wv[k] * ll : 0.f;
+                            g = obs ? wv[k] * (-d.loss_scale * rr * ee) : 0.f;
+                            const float gl = obs ? wv[k] * (d.loss_scale * (1.f - r2e)) : 0.f;
+                            if (d.gls_part) d.gls_part[(int64_t)s * D.dy + pp[k]] = gl;
+                            else if (obs) atomicAdd(d.gacc_logsig + pp[k], (double)gl);
+                        } else {
+                            Lsum += -0.5f * (2.f * lv[k] + rr * rr * ee + GPI_LOG2PI);
+                            g = -d.loss_scale * rr * ee;
+                            const float gl = d.loss_scale * (1.f - rr * rr * ee);
+                            if (d.gls_part) d.gls_part[(int64_t)s * D.dy + pp[k]] = gl;
+                            else atomicAdd(d.gacc_logsig + pp[k], (double)gl);
+                        }
                     } else {
                         g = gv[k];
                     }
@@ -1273,7 +1326,10 @@ struct RomFitLds {   // float offsets after the fp64 block (every block a multip
 
 // Setup, square q: the fp64 sums over its fine free nodes (Y: the sample's row) of W^T Y (4 corners), W^T W
 // (9 entries: 00 11 22 33 01 02 03 13 23) into sq[13], and of |Y|^2 onto cc.
-__device__ __forceinline__ void fit_square_sums(int nc, int r, int q, const float* Y, double& cc, double* sq) {
+// Yw: the sample's row of observation weights, or null.  An entry with weight 0 is never read into a sum
+// (y by a select); weight 1 multiplies exactly, so all-ones weights give the bits of a setup without weights.
+__device__ __forceinline__ void fit_square_sums(int nc, int r, int q, const float* Y, const float* Yw, double& cc,
+                                                double* sq) {
     const int nf = nc * r;
     const int I = q % nc, J = q / nc;
     const int i0 = I == 0 ? 1 : I * r, i1 = (I + 1) * r - 1;     // free columns (inclusive)
@@ -1282,21 +1338,24 @@ __device__ __forceinline__ void fit_square_sums(int nc, int r, int q, const floa
     double pb[4] = {0.0, 0.0, 0.0, 0.0};
     double pg[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int jj = 0; jj < rows; ++jj) {
-        const float* yrow = Y + (int64_t)(J * r + jj) * (nf - 1) - 1;
+        const int64_t ro = (int64_t)(J * r + jj) * (nf - 1) - 1;
+        const float* yrow = Y + ro;
         const double eta = (double)jj * rinv;
         for (int i = i0; i <= i1; ++i) {
-            const double y = (double)yrow[i];
+            const double ow = Yw ? (double)Yw[ro + i] : 1.0;
+            const double y = ow != 0.0 ? (double)yrow[i] : 0.0, yw = ow * y;
             const double xi = (double)(i - I * r) * rinv;
             double w0, w1, w2, w3;                               // corners v0, +x, +y, +x+y
             if (xi >= eta) { w0 = 1.0 - xi; w1 = xi - eta; w2 = 0.0; w3 = eta; }
             else { w0 = 1.0 - eta; w1 = 0.0; w2 = eta - xi; w3 = xi; }
-            cc = fma(y, y, cc);
-            pb[0] = fma(w0, y, pb[0]); pb[1] = fma(w1, y, pb[1]);
-            pb[2] = fma(w2, y, pb[2]); pb[3] = fma(w3, y, pb[3]);
-            pg[0] = fma(w0, w0, pg[0]); pg[1] = fma(w1, w1, pg[1]);
-            pg[2] = fma(w2, w2, pg[2]); pg[3] = fma(w3, w3, pg[3]);
-            pg[4] = fma(w0, w1, pg[4]); pg[5] = fma(w0, w2, pg[5]); pg[6] = fma(w0, w3, pg[6]);
-            pg[7] = fma(w1, w3, pg[7]); pg[8] = fma(w2, w3, pg[8]);
+            const double a0 = ow * w0, a1 = ow * w1, a2 = ow * w2, a3 = ow * w3;
+            cc = fma(yw, y, cc);
+            pb[0] = fma(w0, yw, pb[0]); pb[1] = fma(w1, yw, pb[1]);
+            pb[2] = fma(w2, yw, pb[2]); pb[3] = fma(w3, yw, pb[3]);
+            pg[0] = fma(a0, w0, pg[0]); pg[1] = fma(a1, w1, pg[1]);
+            pg[2] = fma(a2, w2, pg[2]); pg[3] = fma(a3, w3, pg[3]);
+            pg[4] = fma(a0, w1, pg[4]); pg[5] = fma(a0, w2, pg[5]); pg[6] = fma(a0, w3, pg[6]);
+            pg[7] = fma(a1, w3, pg[7]); pg[8] = fma(a2, w3, pg[8]);
         }
     }
 #pragma unroll
@@ -1382,7 +1441,7 @@ __global__ __launch_bounds__(64) void rom_fit_kernel(gpi_rom_fit_desc d, double 
         double* sq = (double*)(slv.m + Solver::STAGE);   // [NQ][13]
         for (int k = 0; k < KQ; ++k) {
             const int q = lane + 64 * k;
-            if (q < NQ) fit_square_sums(NC, r, q, d.Y + s * dy, cc, sq + q * 13);
+            if (q < NQ) fit_square_sums(NC, r, q, d.Y + s * dy, d.y_weight ? d.y_weight + s * d.yw_stride : nullptr, cc, sq + q * 13);
         }
         cc = wave_sum_d(cc);
         Solver::sync();
@@ -1461,7 +1520,10 @@ __global__ __launch_bounds__(64) void rom_fit_kernel(gpi_rom_fit_desc d, double 
 
 template <int NC, int NT>
 void launch_fast(const gpi_rom_desc* d, const RomDims& D, void* stream) {
-    hipLaunchKernelGGL((rom_kernel_fast<NC, NT>), dim3(d->n), dim3(NT), (RomFastLds<NC, NT>::bytes), (hipStream_t)stream, *d, D);
+    if (d->y_weight)
+        hipLaunchKernelGGL((rom_kernel_fast<NC, NT, true>), dim3(d->n), dim3(NT), (RomFastLds<NC, NT>::bytes), (hipStream_t)stream, *d, D);
+    else
+        hipLaunchKernelGGL((rom_kernel_fast<NC, NT, false>), dim3(d->n), dim3(NT), (RomFastLds<NC, NT>::bytes), (hipStream_t)stream, *d, D);
 }
 
 }  // namespace
@@ -1482,8 +1544,9 @@ extern "C" int gpi_rom_fit(const gpi_rom_fit_desc* d, void* stream) {
     if (d->n == 0) return GPI_OK;
     if (!d->Y || !d->F || !d->x || d->x_stride < 2 * d->nc * d->nc || !d->m != !d->v) return GPI_ERR_ARG;
     const int64_t nf = (int64_t)d->nc * d->refine, dy = (nf + 1) * (nf - 1);
-    // d/du of the MSE mean: 2 / (n_total d_y) (G u - b)
-    const double gscale = 2.0 / ((double)(d->n_total ? d->n_total : d->n) * (double)dy);
+    if (!(d->n_obs >= 0.0) || (d->y_weight && d->yw_stride != 0 && d->yw_stride != dy)) return GPI_ERR_ARG;
+    // d/du of the MSE mean: 2 / (n_total d_y) (G u - b); with observation weights 2 / n_obs
+    const double gscale = 2.0 / (d->n_obs > 0.0 ? d->n_obs : (double)(d->n_total ? d->n_total : d->n) * (double)dy);
     if (d->nc == 16)
         hipLaunchKernelGGL(rom_fit_kernel<16>, dim3(d->n), dim3(64), RomFitLds<16>::bytes, (hipStream_t)stream, *d, gscale);
     else if (d->nc == 8)
@@ -1499,6 +1562,11 @@ extern "C" int gpi_rom(const gpi_rom_desc* d, void* stream) {
     if (d->mode == GPI_ROM_LOGLIK && (!d->Y || !d->logsig_y || (!d->gacc_logsig && !d->gls_part) || !d->gx))
         return GPI_ERR_ARG;
     if (d->mode == GPI_ROM_BACKWARD && ((!d->dmu && !d->duc) || !d->gx)) return GPI_ERR_ARG;
+    {   // observation weights: LOGLIK only, one shared row or one row per sample
+        const int64_t nf = (int64_t)d->nc * d->refine;
+        if (d->y_weight && (d->mode != GPI_ROM_LOGLIK || (d->yw_stride != 0 && d->yw_stride != (nf + 1) * (nf - 1))))
+            return GPI_ERR_ARG;
+    }
     if (d->n == 0) return GPI_OK;
     RomDims D;
     D.nc = d->nc;
@@ -1541,7 +1609,8 @@ extern "C" int gpi_rom(const gpi_rom_desc* d, void* stream) {
         GPI_CHECK_LAUNCH();
         return GPI_OK;
     }
-    hipLaunchKernelGGL(rom_kernel, dim3(d->n), dim3(ROM_NT), rom_lds(D).bytes, (hipStream_t)stream, *d, D);
+    if (d->y_weight) hipLaunchKernelGGL(rom_kernel<true>, dim3(d->n), dim3(ROM_NT), rom_lds(D).bytes, (hipStream_t)stream, *d, D);
+    else hipLaunchKernelGGL(rom_kernel<false>, dim3(d->n), dim3(ROM_NT), rom_lds(D).bytes, (hipStream_t)stream, *d, D);
     GPI_CHECK_LAUNCH();
     return GPI_OK;
 }

@@ -108,14 +108,15 @@ class RomDesc(C.Structure):
                 ('x', vp), ('x_stride', i64), ('F', vp), ('mu_y', vp), ('Y', vp), ('logsig_y', vp),
                 ('loss_scale', f32), ('gx_accumulate', i32), ('dmu', vp), ('duc', vp), ('gx', vp), ('gx_stride', i64),
                 ('gacc_logsig', vp), ('loss_acc', vp), ('flag', vp), ('uc', vp), ('gls_part', vp),
-                ('x_mu', vp), ('x_ls', vp), ('x_eps', vp)]
+                ('x_mu', vp), ('x_ls', vp), ('x_eps', vp), ('y_weight', vp), ('yw_stride', i64)]
 
 
 class RomFitDesc(C.Structure):
     _fields_ = [('nc', i32), ('refine', i32), ('n', i32), ('iters', i32), ('n_total', i64),
                 ('Y', vp), ('F', vp), ('x', vp), ('x_stride', i64), ('m', vp), ('v', vp), ('step0', i64),
                 ('lr', f32), ('beta1', f32), ('beta2', f32), ('eps', f32),
-                ('sumsq', vp), ('ynorm2', vp), ('x_eval', vp), ('uc', vp), ('flag', vp)]
+                ('sumsq', vp), ('ynorm2', vp), ('x_eval', vp), ('uc', vp), ('flag', vp),
+                ('y_weight', vp), ('yw_stride', i64), ('n_obs', C.c_double)]
 
 
 CGR_AUTO, CGR_BAND, CGR_STREAM, CGR_GENERAL = 0, 1, 2, 3

@@ -216,7 +216,7 @@ class ElboEngine(object):
     from the VO posterior); vo_holdoff keeps only its logL_x - KL part (generative.py:349-364)."""
 
     def __init__(self, model, B_u, N_s, normalize=False, N_vo=0, vo_holdoff=False, q_unsup=None,
-                 running_modules=None, shared_grads=True):
+                 running_modules=None, shared_grads=True, y_weight=None):
         """q_unsup: q_z['unsupervised'] for the non-armortized unsupervised term (no encoder,
         GenerativeModel.elbo_unsupervised generative.py:515-544): its rows replace the encoder
         heads; the term's KL is the reference's KLD of q_z['supervised'] (sic, :525).
@@ -465,6 +465,11 @@ class ElboEngine(object):
             r.mu_y = None
             r.uc = None
             r.dmu = None
+            if slot == T_LOGL_Y and self.y_weight is not None:
+                # partially observed labels: the supervised launch alone (virtual observables are complete);
+                # the unobserved entries' d/dlogsigma_y rows are zeros, so the reduce item below is unchanged
+                r.y_weight = self.y_weight.data_ptr()
+                r.yw_stride = self.d_y if self.y_weight.dim() == 2 else 0
             key = 'sup' if slot == T_LOGL_Y else 'vo'
             r.gls_part = ws.t_parts.data_ptr() + 4 * self.gls_off[key]
             it = L.ReduceItem()
@@ -474,6 +479,15 @@ class ElboEngine(object):
             return r
 
         self.rom_reduce = []
+        # observation weights of the labelled term (GenerativeModel.label_weights): fp32 [d_y] shared or
+        # [N_s, d_y]; the descriptor holds the tensor's address, the engine keeps the tensor
+        if y_weight is not None:
+            L.require_device(y_weight)
+            if y_weight.dtype != torch.float32 or not y_weight.is_contiguous() or \
+                    tuple(y_weight.shape) not in ((self.d_y,), (self.N_s, self.d_y)):
+                raise ValueError('y_weight: contiguous fp32 [%d] or [%d, %d], got %s %s'
+                                 % (self.d_y, self.N_s, self.d_y, y_weight.dtype, tuple(y_weight.shape)))
+        self.y_weight = y_weight if self.N_s > 0 else None
         # GPI_ROM_EARLY=1 (free q_X only): the fused step's ROM runs at the very start of the step on
         # the side stream, its inputs drawn from q_X in the kernel, concurrently with the encoder
         # (not with the MLP map, whose forward runs ahead of the ROM on the side stream and needs the head's z)
@@ -1255,8 +1269,9 @@ def ROM_NN(nc):
 
 def rom_call(nc, refine, x, F, input_kappa, mode, mu_y=None, uc=None, dmu=None, duc=None, gx=None, Y=None,
              logsig_y=None, gacc_logsig=None, loss_acc=None, flag=None, loss_scale=1.0, gx_accumulate=False,
-             gls_part=None):
-    """Thin launcher of gpi_rom for the standalone ROM / ReducedOrderModelOperator."""
+             gls_part=None, y_weight=None, yw_stride=None):
+    """Thin launcher of gpi_rom for the standalone ROM / ReducedOrderModelOperator.  y_weight (LOGLIK): fp32
+    observation weights, [d_y] shared or [n, d_y] (yw_stride overrides the stride taken from its shape)."""
     for t in (x, F):
         L.require_device(t)
     r = L.RomDesc()
@@ -1267,6 +1282,10 @@ def rom_call(nc, refine, x, F, input_kappa, mode, mu_y=None, uc=None, dmu=None, 
     r.gx_stride = gx.stride(0) if gx is not None else 0
     r.gacc_logsig, r.loss_acc, r.flag, r.gls_part = p(gacc_logsig), p(loss_acc), p(flag), p(gls_part)
     r.loss_scale, r.gx_accumulate = loss_scale, 1 if gx_accumulate else 0
+    if y_weight is not None:
+        L.require_device(y_weight)
+        r.y_weight = y_weight.data_ptr()
+        r.yw_stride = (y_weight.stride(0) if y_weight.dim() == 2 else 0) if yw_stride is None else yw_stride
     _run(_lib().gpi_rom, C.byref(r), L.stream_handle(), what='rom')
 
 

@@ -103,6 +103,11 @@ class FusedElboStep(object):
                 raise L.NativeError('FusedElboStep: the VO ensemble must keep fp32 mean / logsigma buffers')
             self._vo_ptrs = tuple(t.data_ptr() for t in vo_buffers(self.vo))
         self.normalize = normalize
+        # partially observed labels: the model's observation weights as they stand now.  The step (and its
+        # captured graphs) holds this tensor's address: an in-place edit is seen by the next step, another
+        # tensor needs a new step (_check_label_mask).  Data parallel: the labelled shard and its mask are
+        # rank-local, nothing is exchanged.
+        self._yw = model.label_weights(self.N_s) if self.N_s else None
         if subset_seed is None and self.world > 1 and self.B_u > 0:
             # every rank must draw the SAME global permutation (its B_u-slice of it); the per-rank
             # noise seed would give overlapping / duplicated slices without any error
@@ -217,9 +222,21 @@ class FusedElboStep(object):
     # ------------------------------------------------------------------
     def _new_engine(self, vo_holdoff):
         if not self.N_vo:
-            return ElboEngine(self.model, self.B_u, self.N_s, normalize=self.normalize)
+            return ElboEngine(self.model, self.B_u, self.N_s, normalize=self.normalize, y_weight=self._yw)
         return ElboEngine(self.model, self.B_u, self.N_s, normalize=self.normalize, N_vo=self.N_vo,
-                          vo_holdoff=vo_holdoff)
+                          vo_holdoff=vo_holdoff, y_weight=self._yw)
+
+    def _check_label_mask(self):
+        """Raise when the model's label mask is no longer the tensor this step was built on (set, cleared or
+        replaced since): the launches read the old one."""
+        if not self.N_s:
+            return
+        now = self.model.label_weights(self.N_s)
+        if (now is None) != (self._yw is None) or (now is not None and (
+                now.data_ptr() != self._yw.data_ptr() or tuple(now.shape) != tuple(self._yw.shape))):
+            raise L.NativeError('FusedElboStep: the model\'s label mask (preprocess_y_fct / set_label_mask) was '
+                                'set, cleared or replaced after the step was built; the step (and its captured '
+                                'graphs) reads the old one: rebuild the step.  Edit a mask in place instead.')
 
     def _set_sync_bn(self, engine):
         pg = self.pg
@@ -408,6 +425,7 @@ class FusedElboStep(object):
         self.optimizer._opt_called = True
 
     def step_eager(self):
+        self._check_label_mask()
         self._check_stream_pair()
         fused = self.fuse_adam
         self._forward_backward(epilogue=not fused)
@@ -680,6 +698,7 @@ class FusedElboStep(object):
             self._post_error_copy()
 
     def _step(self):
+        self._check_label_mask()
         self.sync_lr()
         if self.graph is None:
             return self.step_eager()
@@ -706,6 +725,7 @@ class FusedElboStep(object):
         """n steps: with capture(unroll=k), n // k replays of the k-step graphs, then single steps."""
         n = int(n)
         self._poll_error()
+        self._check_label_mask()
         if self.graph is not None and self.unroll > 1 and self.g_fb_k is not None:
             self.sync_lr()
             self._check_stream_pair()

@@ -248,6 +248,13 @@ typedef struct gpi_rom_desc {
     const float* x_mu;         /* x_draw: [n, 2 nc^2] q_X means, log-sigmas and noise */
     const float* x_ls;
     const float* x_eps;
+    const float* y_weight;     /* optional (LOGLIK only, GPI_ERR_ARG in any other mode): observation weights of the
+                                  label entries, w in {0, 1}.  NULL: every entry is observed.  An entry with w == 0
+                                  contributes exactly 0 to loss_acc, gx and the d/d logsigma_y rows whatever Y holds
+                                  there (NaN and Inf included: a select, not only a product); mu_y is written at
+                                  every node.  All-ones weights give the bits of a launch without weights. */
+    int64_t yw_stride;         /* 0: one [d_y] row shared by the n samples; d_y: rows [n, d_y].  Anything else:
+                                  GPI_ERR_ARG */
 } gpi_rom_desc;
 
 /* Optimal effective properties (OptimizeEffectiveProperties, bottleneck/utils.py:250-282): per sample n,
@@ -282,6 +289,13 @@ typedef struct gpi_rom_fit_desc {
     float* uc;                 /* optional [n, (nc+1)^2]: the coarse solution of that evaluation */
     int32_t* flag;             /* optional: set to 1 when a sample meets kappa <= 1e-12 or a non-finite residual;
                                   the other samples are unaffected */
+    const float* y_weight;     /* optional observation weights of the label entries, w in {0, 1} (gpi_rom_desc's):
+                                  J = 1 / n_obs sum_n sum_p w (W u(x_n) - Y_n)_p^2, i.e. G = W^T diag(w) W,
+                                  b = W^T diag(w) Y, c = sum w Y^2 in the setup pass (per sample, as they already
+                                  are); the iterations are untouched.  Y is never read into a sum where w == 0.
+                                  sumsq and ynorm2 are then over the observed entries. */
+    int64_t yw_stride;         /* 0: one shared [d_y] row; d_y: rows [n, d_y]; anything else: GPI_ERR_ARG */
+    double n_obs;              /* observed entries of the WHOLE batch (the mean's denominator); 0: n_total d_y */
 } gpi_rom_fit_desc;
 
 /* Coarse-grained residual on the fine grid (VirtualObservables CGR query,

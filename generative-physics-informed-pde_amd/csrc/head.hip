@@ -1433,22 +1433,27 @@ int head_family(const gpi_head_desc* d) {
 }
 
 // the MFMA kernels' preconditions: widths that fit the LDS row buffers, float4-aligned rows
+bool head_mfma_gate(const gpi_head_desc* d) {
+    if (d->flags & GPI_HEAD_VALU) return false;
+    const bool enc = (d->flags & GPI_HEAD_ENC) && d->n_enc > 0;
+    if (d->d_z > MZ || (d->d_z & 3) || d->d_lat > MW || (d->d_lat & 3) || d->d_x > MW || (d->d_x & 3)) return false;
+    if (enc && (d->d_feat > MW || (d->d_feat & 3))) return false;
+    const bool gp = ((d->flags | d->flags2) & GPI_HEAD_GP) != 0;   // the forward's float4 reads of gp_w
+    const int64_t offs[] = {enc ? d->fc_w : 0, enc ? d->mu_w : 0, enc ? d->ls_w : 0, enc ? d->feat : 0,
+                            enc ? d->gfeat : 0, enc ? d->hpre : 0, enc ? d->dhpre : 0,
+                            (d->flags & GPI_HEAD_LATENT) ? d->lat_w : 0, (d->flags & GPI_HEAD_LATENT) ? d->lat : 0,
+                            (d->flags & GPI_HEAD_LATENT) ? d->glat : 0, gp ? d->gp_w : 0, d->zmu, d->zls, d->gz};
+    for (int64_t o : offs)
+        if (o & 3) return false;
+    return true;
+}
+
 bool head_mfma_ok(const gpi_head_desc* d) {
     static const int on = [] {
         const char* v = getenv("GPI_HEAD_MFMA");
         return v && *v ? atoi(v) : 1;
     }();
-    if (!on || (d->flags & GPI_HEAD_VALU)) return false;
-    const bool enc = (d->flags & GPI_HEAD_ENC) && d->n_enc > 0;
-    if (d->d_z > MZ || (d->d_z & 3) || d->d_lat > MW || (d->d_lat & 3) || d->d_x > MW || (d->d_x & 3)) return false;
-    if (enc && (d->d_feat > MW || (d->d_feat & 3))) return false;
-    const int64_t offs[] = {enc ? d->fc_w : 0, enc ? d->mu_w : 0, enc ? d->ls_w : 0, enc ? d->feat : 0,
-                            enc ? d->gfeat : 0, enc ? d->hpre : 0, enc ? d->dhpre : 0,
-                            (d->flags & GPI_HEAD_LATENT) ? d->lat_w : 0, (d->flags & GPI_HEAD_LATENT) ? d->lat : 0,
-                            (d->flags & GPI_HEAD_LATENT) ? d->glat : 0, d->zmu, d->zls, d->gz};
-    for (int64_t o : offs)
-        if (o & 3) return false;
-    return true;
+    return on && head_mfma_gate(d);
 }
 
 bool head_ok(const gpi_head_desc* d) {
@@ -1458,6 +1463,13 @@ bool head_ok(const gpi_head_desc* d) {
 }
 
 }  // namespace
+
+extern "C" int gpi_head_form(const gpi_head_desc* d, int prefetch) {
+    if (!head_ok(d)) return GPI_ERR_ARG;
+    if (!head_mfma_gate(d)) return 0;
+    const int fam = prefetch ? head_family(d) : 0;
+    return fam ? 1 + fam : 1;
+}
 
 extern "C" int gpi_head_forward(const gpi_head_desc* d, const float* params, float* ws, void* stream) {
     if (!head_ok(d) || !params || !ws) return GPI_ERR_ARG;

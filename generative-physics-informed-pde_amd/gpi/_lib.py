@@ -281,6 +281,7 @@ SIGNATURES = {
     'gpi_wgrad_reduce': (C.c_int, [C.POINTER(ReduceItem), C.c_int, vp, vp, vp]),
     'gpi_head_forward': (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp]),
     'gpi_head_backward': (C.c_int, [C.POINTER(HeadDesc), vp, vp, vp, vp]),
+    'gpi_head_form': (C.c_int, [C.POINTER(HeadDesc), C.c_int]),
     'gpi_outer_gemm': (C.c_int, [C.POINTER(GemmItem), C.c_int, vp, vp, vp]),
     'gpi_rom': (C.c_int, [C.POINTER(RomDesc), vp]),
     'gpi_rom_fit': (C.c_int, [C.POINTER(RomFitDesc), vp]),

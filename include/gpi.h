@@ -694,6 +694,12 @@ int gpi_wgrad_reduce(const gpi_reduce_item* items, int n_items, const float* wpa
 
 int gpi_head_forward(const gpi_head_desc* d, const float* params, float* ws, void* stream);
 int gpi_head_backward(const gpi_head_desc* d, const float* params, float* ws, double* gacc, void* stream);
+/* The kernel form gpi_head_forward / _backward launch for a descriptor: 0 the per-sample VALU kernels, 1 the
+ * generic 16-sample MFMA tiles, 2 / 3 the prefetched MFMA form for the widths 80/64/64/128 / 64/16/64/32
+ * (GPI_ERR_ARG for a descriptor the launchers refuse).  The launchers' own width / alignment gate decides;
+ * `prefetch` stands in for GPI_HEAD_PREFETCH (0: never the prefetched form) and GPI_HEAD_MFMA counts as unset,
+ * so the answer is a function of the descriptor alone.  No device work. */
+int gpi_head_form(const gpi_head_desc* d, int prefetch);
 
 int gpi_outer_gemm(const gpi_gemm_item* items, int n_items, const float* ws, double* gacc, void* stream);
 

@@ -28,7 +28,8 @@ def lib():
 def test_header_declares_the_entry_points():
     names = declared()
     for n in ('gpi_conv_forward', 'gpi_conv_backward', 'gpi_codec_forward', 'gpi_codec_backward', 'gpi_rom',
-              'gpi_cgr_residual', 'gpi_adam', 'gpi_head_forward', 'gpi_head_backward', 'gpi_wgrad_reduce'):
+              'gpi_cgr_residual', 'gpi_adam', 'gpi_head_forward', 'gpi_head_backward', 'gpi_head_form',
+              'gpi_wgrad_reduce'):
         assert n in names
 
 

@@ -10,10 +10,12 @@
 // MFMA has the same peak rate and the same chain numerics; here the work is a few MFLOP per step and the odd
 // widths would need padded operand images).
 //
-// The forward's last layer keeps mu_X in registers and finishes the gp term per element exactly as head.hip
-// does (X~, logL_X, entropy); the backward starts from the same per-element expressions (dJ/dmu_X, the q_X
-// rows' and logsigmas_X's gradients) and ends by adding W_1^T delta_1 to the q_z rows' gradients.
+// The forward's last layer keeps mu_X in registers and finishes the gp term per element with head.hip's own
+// expressions (dense_terms.h: X~, logL_X, entropy); the backward starts from the same header's per-element
+// gradients (dJ/dmu_X, the q_X rows' and logsigmas_X's) and ends by adding W_1^T delta_1 to the q_z rows'
+// gradients (that tail has no KL term: its own expression, not the header's).
 #include "common.h"
+#include "dense_terms.h"
 
 using namespace gpi;
 
@@ -190,12 +192,10 @@ __global__ __launch_bounds__(NT) void gpmlp_fwd_kernel(gpi_gpmlp_desc d, const f
         const Seg sg = seg_of(d, q);
         const int64_t pi = (int64_t)sg.row * dx + t;            // q_X parameter row
         const float lsq = P[sg.qx_ls + pi];
-        const float xs = fmaf(expf(lsq), ws[d.eps_x + qi], P[sg.qx_mu + pi]);
+        const GpElemFwd E(P[sg.qx_mu + pi], lsq, ws[d.eps_x + qi]);
         ws[d.mux + qi] = a;
-        ws[d.xs + qi] = xs;
-        const float gls = P[d.gp_ls + t];
-        const float r = xs - a;
-        const float lx = -0.5f * (2.f * gls + r * r * expf(-2.f * gls) + GPI_LOG2PI);
+        ws[d.xs + qi] = E.xs;
+        const float lx = E.loglik(a, P[d.gp_ls + t]);
         acc4[0] += sg.second ? 0.f : lx;
         acc4[1] += sg.second ? 0.f : lsq;
         acc4[2] += sg.second ? lx : 0.f;
@@ -254,17 +254,15 @@ __global__ __launch_bounds__(NT) void gpmlp_bwd_kernel(gpi_gpmlp_desc d, const f
             const Seg sg = seg_of(d, q);
             const int64_t pi = (int64_t)sg.row * dx + t;
             const float gls = P[d.gp_ls + t];
-            const float e2 = expf(-2.f * gls);
-            const float xs = ws[d.xs + qi], mux = ws[d.mux + qi];
-            const float r = xs - mux;
-            const float gm = -sg.lx_scale * r * e2;             // dJ/dmu_X
+            const GpElemBwd G(ws[d.xs + qi], ws[d.mux + qi], gls, sg.lx_scale);
+            const float gm = G.gmux();
             bufA[si * pA + t] = gm;
             ws[d.gmux + qi] = gm;
-            gls_sum += (double)(sg.lx_scale * (1.f - r * r * e2));
-            const float dxs = ws[d.gxs + qi] + sg.lx_scale * r * e2;   // dJ/dX~
+            gls_sum += (double)G.gls();
+            const float dxs = G.gqx_mu(ws[d.gxs + qi]);
             const float lsq = P[sg.qx_ls + pi];
             atomicAdd(gacc + sg.qx_mu + pi, (double)dxs);
-            atomicAdd(gacc + sg.qx_ls + pi, (double)(dxs * expf(lsq) * ws[d.eps_x + qi] - sg.lx_scale));
+            atomicAdd(gacc + sg.qx_ls + pi, (double)G.gqx_ls(dxs, lsq, ws[d.eps_x + qi]));
         }
         if (!lockx) atomicAdd(gacc + d.gp_ls + t, gls_sum);
     }

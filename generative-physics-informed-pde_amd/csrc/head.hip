@@ -10,7 +10,21 @@
 // The backward writes per-sample deltas; the shared-weight gradients
 // (sum over samples of delta (x) input) are formed by gpi_outer_gemm, the
 // per-sample variational parameters' gradients are written directly.
+//
+// Layout of this file.  The chain exists in three kernel forms, all reachable (gpi_head_form):
+//   head_fwd_kernel / head_bwd_kernel      one workgroup per sample, VALU mat-vecs; any width <= VMAX; the parity
+//                                          reference of the other two (GPI_HEAD_VALU, GPI_HEAD_MFMA=0)
+//   head_fwd_mfma / head_bwd_mfma          16-sample tiles on the matrix cores, each stage's weights loaded in turn
+//   head_fwd_mfma2 / head_bwd_mfma2<...>   the same tiles with every global operand issued at entry, for the width
+//                                          families of FAMILIES
+// with outer_gemm_kernel / outer_gemm_mfma for the shared-weight gradients.  What the forms have in common is stated
+// once: the per-element expressions (z draw + KL, gp term forward / backward, the (dmu, dlogsigma) pair) in
+// dense_terms.h, shared with gpmlp.hip; the variational segment of a row (qseg); the MFMA A-operand fetch (aload,
+// under contract<> and wload<>); the tile's term sums into the replica slots (publish_kl, publish_lx); and on the
+// host one descriptor -> form map (head_form) and one family table.  Each form keeps its own operand fetch (global
+// memory at use, LDS rows, or registers prefetched at entry) and its own reductions: those are the forms.
 #include "common.h"
+#include "dense_terms.h"
 #include <stdlib.h>
 
 using namespace gpi;
@@ -219,12 +233,11 @@ __global__ __launch_bounds__(HT) void head_fwd_kernel(gpi_head_desc d, const flo
         if (d.flags & GPI_HEAD_REPARAM) {
             float kl = 0.f;
             for (int k = tid; k < dz; k += HT) {
-                const float mu = v0[k], ls = v3[k];
-                const float e = expf(ls);
-                const float zz = fmaf(e, ws[d.eps_z + (int64_t)s * dz + k], mu);
+                const ZDraw D(v0[k], v3[k]);
+                const float zz = D.z(ws[d.eps_z + (int64_t)s * dz + k]);
                 z[k] = zz;
                 ws[d.z + (int64_t)s * dz + k] = zz;
-                kl += 1.f + 2.f * ls - mu * mu - e * e;
+                kl += D.kl();
             }
             kl = block_sum128(kl, scratch);
             if (tid == 0) atomicAdd(d.terms + 0 * GPI_REPLICAS + blockIdx.x % GPI_REPLICAS, -0.5 * (double)kl);
@@ -235,12 +248,11 @@ __global__ __launch_bounds__(HT) void head_fwd_kernel(gpi_head_desc d, const flo
         if (g.flags & GPI_HEAD_QZ) {
             float kl = 0.f;
             for (int k = tid; k < dz; k += HT) {
-                const float mu = P[g.qz_mu + (int64_t)g.row * dz + k], ls = P[g.qz_ls + (int64_t)g.row * dz + k];
-                const float e = expf(ls);
-                const float zz = fmaf(e, ws[d.eps_z + (int64_t)s * dz + k], mu);
+                const ZDraw D(P[g.qz_mu + (int64_t)g.row * dz + k], P[g.qz_ls + (int64_t)g.row * dz + k]);
+                const float zz = D.z(ws[d.eps_z + (int64_t)s * dz + k]);
                 z[k] = zz;
                 ws[d.z + (int64_t)s * dz + k] = zz;
-                kl += 1.f + 2.f * ls - mu * mu - e * e;
+                kl += D.kl();
             }
             kl = block_sum128(kl, scratch);
             if (tid == 0) atomicAdd(g.terms + 0 * GPI_REPLICAS + blockIdx.x % GPI_REPLICAS, -0.5 * (double)kl);
@@ -271,12 +283,10 @@ __global__ __launch_bounds__(HT) void head_fwd_kernel(gpi_head_desc d, const flo
             }
             const int64_t pi = (int64_t)g.row * d.d_x + t;          // q_X parameter row
             const float lsq = P[g.qx_ls + pi];
-            const float xs = fmaf(expf(lsq), ws[d.eps_x + qi], P[g.qx_mu + pi]);
+            const GpElemFwd E(P[g.qx_mu + pi], lsq, ws[d.eps_x + qi]);
             ws[d.mux + qi] = a;
-            ws[d.xs + qi] = xs;
-            const float gls = P[d.gp_ls + t];
-            const float r = xs - a;
-            lx += -0.5f * (2.f * gls + r * r * expf(-2.f * gls) + GPI_LOG2PI);
+            ws[d.xs + qi] = E.xs;
+            lx += E.loglik(a, P[d.gp_ls + t]);
             ent += lsq;
         }
         if (lockx) return;
@@ -324,17 +334,15 @@ __global__ __launch_bounds__(HT) void head_bwd_kernel(gpi_head_desc d, const flo
             }
             const int64_t pi = (int64_t)g.row * d.d_x + t;
             const float gls = P[d.gp_ls + t];
-            const float e2 = expf(-2.f * gls);
-            const float xs = ws[d.xs + qi], mux = ws[d.mux + qi];
-            const float r = xs - mux;
-            const float gm = -g.lx_scale * r * e2;            // dJ/dmu_X
+            const GpElemBwd G(ws[d.xs + qi], ws[d.mux + qi], gls, g.lx_scale);
+            const float gm = G.gmux();
             v2[t] = gm;
             ws[d.gmux + qi] = gm;
-            atomicAdd(gacc + d.gp_ls + t, (double)(g.lx_scale * (1.f - r * r * e2)));
-            const float dxs = ws[d.gxs + qi] + g.lx_scale * r * e2;   // dJ/dX~
+            atomicAdd(gacc + d.gp_ls + t, (double)G.gls());
+            const float dxs = G.gqx_mu(ws[d.gxs + qi]);
             const float lsq = P[g.qx_ls + pi];
             gacc[g.qx_mu + pi] += (double)dxs;
-            gacc[g.qx_ls + pi] += (double)(dxs * expf(lsq) * ws[d.eps_x + qi] - g.lx_scale);
+            gacc[g.qx_ls + pi] += (double)G.gqx_ls(dxs, lsq, ws[d.eps_x + qi]);
         }
         __syncthreads();
         matvec_t2(P + d.gp_w, v2, d.d_x, P, v2, 0, dz, dz_, true, part);
@@ -346,10 +354,9 @@ __global__ __launch_bounds__(HT) void head_bwd_kernel(gpi_head_desc d, const flo
             for (int k = tid; k < dz; k += HT) {
                 const int64_t qi = (int64_t)g.row * dz + k;
                 const float mu = P[g.qz_mu + qi], ls = P[g.qz_ls + qi];
-                const float e = expf(ls);
-                gacc[g.qz_mu + qi] += (double)(dz_[k] + g.kl_scale * mu);
-                gacc[g.qz_ls + qi] += (double)(dz_[k] * e * ws[d.eps_z + (int64_t)s * dz + k] +
-                                               g.kl_scale * (e * e - 1.f));
+                const ZDrawBwd G(ls, g.kl_scale);
+                gacc[g.qz_mu + qi] += (double)G.dmu(dz_[k], mu);
+                gacc[g.qz_ls + qi] += (double)G.dls(dz_[k], ws[d.eps_z + (int64_t)s * dz + k]);
             }
         }
         return;
@@ -360,9 +367,9 @@ __global__ __launch_bounds__(HT) void head_bwd_kernel(gpi_head_desc d, const flo
         float dmu = dz_[k], dls = 0.f;
         const float mu = ws[d.zmu + (int64_t)s * dz + k], ls = ws[d.zls + (int64_t)s * dz + k];
         if (d.flags & GPI_HEAD_REPARAM) {
-            const float e = expf(ls);
-            dls = dz_[k] * e * ws[d.eps_z + (int64_t)s * dz + k] + d.kl_scale_enc * (e * e - 1.f);
-            dmu += d.kl_scale_enc * mu;
+            const ZDrawBwd G(ls, d.kl_scale_enc);
+            dls = G.dls(dz_[k], ws[d.eps_z + (int64_t)s * dz + k]);
+            dmu = G.dmu(dmu, mu);
         } else {
             dls = ws[d.dzls + (int64_t)s * dz + k];   // caller-provided d/dlogsigma
         }
@@ -466,9 +473,28 @@ __device__ __forceinline__ hf32x4 mfma16(float a, float b, hf32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// Lane (i, g)'s A operand of output block jb (< 0: zeros) of a J x K product for the 16-wide chunk at k0:
+// A(16 jb + i, k0 + 4 g + t), t = 0..3.  Rows j >= J and chunks k >= K read 0.
+// WT = false: A(j, k) = W[j K + k] (a torch Linear weight [J][K], rows 16-byte aligned: flat.py), one float4;
+// WT = true:  A(j, k) = W[k J + j] (the transposed product with a [K][J] weight).
+template <bool WT>
+__device__ __forceinline__ hf32x4 aload(const float* __restrict__ W, int J, int K, int jb, int k0) {
+    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    const int j = 16 * jb + i, k = k0 + 4 * g;
+    hf32x4 a{0.f, 0.f, 0.f, 0.f};
+    if (jb >= 0 && j < J && k < K) {
+        // (32-bit element offsets from the uniform matrix base: scalar base + one VGPR per load)
+        if constexpr (!WT) {
+            a = *reinterpret_cast<const hf32x4*>(W + (j * K + k));
+        } else {
+            const int o = k * J + j;
+            a = hf32x4{W[o], W[o + J], W[o + 2 * J], W[o + 3 * J]};
+        }
+    }
+    return a;
+}
+
 // acc[u] += A(16 jb[u] + i, k) X[i][k] over k < K for the NB blocks jb[u] (< 0: skipped) of one matrix.
-// WT = false: A(j, k) = W[j K + k] (a torch Linear weight [J][K], rows 16-byte aligned: flat.py);
-// WT = true:  A(j, k) = W[k J + j] (the transposed product with a [K][J] weight).  Rows j >= J read 0.
 template <bool WT, int NB>
 __device__ __forceinline__ void contract(const float* __restrict__ W, int J, int K, const int (&jb)[NB],
                                          const float* X, int px, hf32x4 (&acc)[NB]) {
@@ -477,22 +503,8 @@ __device__ __forceinline__ void contract(const float* __restrict__ W, int J, int
         hf32x4 a[NB][KC];
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
-            const int j = 16 * jb[u] + i;
-            const bool jok = jb[u] >= 0 && j < J;
 #pragma unroll
-            for (int c = 0; c < KC; ++c) {
-                const int k = c0 + 16 * c + 4 * g;
-                a[u][c] = hf32x4{0.f, 0.f, 0.f, 0.f};
-                if (jok && k < K) {
-                    // (32-bit element offsets from the uniform matrix base: scalar base + one VGPR per load)
-                    if constexpr (!WT) {
-                        a[u][c] = *reinterpret_cast<const hf32x4*>(W + (j * K + k));
-                    } else {
-                        const int o = k * J + j;
-                        a[u][c] = hf32x4{W[o], W[o + J], W[o + 2 * J], W[o + 3 * J]};
-                    }
-                }
-            }
+            for (int c = 0; c < KC; ++c) a[u][c] = aload<WT>(W, J, K, jb[u], c0 + 16 * c);
         }
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
@@ -560,8 +572,44 @@ __device__ __forceinline__ HTile head_tile(const gpi_head_desc& d, int t) {
     return T;
 }
 
-__device__ __forceinline__ void zero_lds(float* p, int n) {   // n: multiple of 4, p 16-byte aligned
-    for (int e = threadIdx.x; e < n / 4; e += 256) reinterpret_cast<float4*>(p)[e] = float4{0.f, 0.f, 0.f, 0.f};
+template <int NT>   // threads of the workgroup; n: multiple of 4, p 16-byte aligned
+__device__ __forceinline__ void zero_lds(float* p, int n) {
+    for (int e = threadIdx.x; e < n / 4; e += NT) reinterpret_cast<float4*>(p)[e] = float4{0.f, 0.f, 0.f, 0.f};
+}
+
+// The variational tile T holds samples of segment 1 (h = 0) / of segment 2 (h = 1).
+__device__ __forceinline__ bool tile_has_seg(const gpi_head_desc& d, const HTile& T, int h) {
+    const int qa = T.s0 - d.n_enc;
+    return h ? qa + T.n > d.n_q : qa < d.n_q;
+}
+
+// Thread 0 adds a tile's block-reduced KL sums to the replica slots: red[0] is the encoder tile's (with the
+// reparametrisation) or segment 1's q_z sum, red[1] segment 2's.
+__device__ __forceinline__ void publish_kl(const gpi_head_desc& d, const HTile& T, const float* red) {
+    if (threadIdx.x != 0) return;
+    const int r = blockIdx.x % GPI_REPLICAS;
+    if (T.enc) {
+        if (d.flags & GPI_HEAD_REPARAM) atomicAdd(d.terms + 0 * GPI_REPLICAS + r, -0.5 * (double)red[0]);
+    } else {
+        if (tile_has_seg(d, T, 0) && (d.flags & GPI_HEAD_QZ)) atomicAdd(d.terms + GPI_REPLICAS + r, -0.5 * (double)red[0]);
+        if (tile_has_seg(d, T, 1) && (d.flags2 & GPI_HEAD_QZ)) atomicAdd(d.terms2 + r, -0.5 * (double)red[1]);
+    }
+}
+
+// Thread 0 adds a variational tile's block-reduced (logL_X, entropy) sums to the replica slots: red[0..1]
+// segment 1's, red[2..3] segment 2's.  lx1 / lx2: the segment has samples in the tile, the gp term and a free X
+// (each forward forms them from the flags it holds in registers anyway).
+__device__ __forceinline__ void publish_lx(const gpi_head_desc& d, bool lx1, bool lx2, const float* red) {
+    if (threadIdx.x != 0) return;
+    const int r = blockIdx.x % GPI_REPLICAS;
+    if (lx1) {
+        atomicAdd(d.terms + 2 * GPI_REPLICAS + r, (double)red[0]);
+        atomicAdd(d.terms + 3 * GPI_REPLICAS + r, (double)red[1]);
+    }
+    if (lx2) {
+        atomicAdd(d.terms2 + 1 * GPI_REPLICAS + r, (double)red[2]);
+        atomicAdd(d.terms2 + 2 * GPI_REPLICAS + r, (double)red[3]);
+    }
 }
 
 // rows s0 .. s0 + n of a [*, w] workspace matrix into LDS rows (pitch px), w % 4 == 0
@@ -581,11 +629,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
     const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
     const HTile T = head_tile(d, blockIdx.x);
     const int dz = d.d_z, df = d.d_feat;
-    zero_lds(sX, TS * LPW);
-    zero_lds(sH, TS * LPW);
-    zero_lds(sMU, TS * LPZ);
-    zero_lds(sLS, TS * LPZ);
-    zero_lds(sZ, TS * LPZ);
+    zero_lds<256>(sX, TS * LPW);
+    zero_lds<256>(sH, TS * LPW);
+    zero_lds<256>(sMU, TS * LPZ);
+    zero_lds<256>(sLS, TS * LPZ);
+    zero_lds<256>(sZ, TS * LPZ);
     __syncthreads();
     float kl[2] = {0.f, 0.f};   // per variational segment (encoder tile: [0])
     if (T.enc) {
@@ -633,12 +681,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
             const int si = e / dz, k = e - si * dz;
             const int64_t o = (int64_t)(T.s0 + si) * dz + k;
             if (d.flags & GPI_HEAD_REPARAM) {
-                const float mu = sMU[si * LPZ + k], ls = sLS[si * LPZ + k];
-                const float ex = expf(ls);
-                const float zz = fmaf(ex, ws[d.eps_z + o], mu);
+                const ZDraw D(sMU[si * LPZ + k], sLS[si * LPZ + k]);
+                const float zz = D.z(ws[d.eps_z + o]);
                 sZ[si * LPZ + k] = zz;
                 ws[d.z + o] = zz;
-                kl[0] += 1.f + 2.f * ls - mu * mu - ex * ex;
+                kl[0] += D.kl();
             } else {
                 sZ[si * LPZ + k] = ws[d.z + o];
             }
@@ -649,12 +696,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
             const int s = T.s0 + si, q = s - d.n_enc;
             const QSeg sg = qseg(d, q);
             if (sg.flags & GPI_HEAD_QZ) {
-                const float mu = P[sg.qz_mu + (int64_t)sg.row * dz + k], ls = P[sg.qz_ls + (int64_t)sg.row * dz + k];
-                const float ex = expf(ls);
-                const float zz = fmaf(ex, ws[d.eps_z + (int64_t)s * dz + k], mu);
+                const ZDraw D(P[sg.qz_mu + (int64_t)sg.row * dz + k], P[sg.qz_ls + (int64_t)sg.row * dz + k]);
+                const float zz = D.z(ws[d.eps_z + (int64_t)s * dz + k]);
                 sZ[si * LPZ + k] = zz;
                 ws[d.z + (int64_t)s * dz + k] = zz;
-                kl[q >= d.n_q] += 1.f + 2.f * ls - mu * mu - ex * ex;
+                kl[q >= d.n_q] += D.kl();
             } else {
                 sZ[si * LPZ + k] = ws[d.z + (int64_t)s * dz + k];
             }
@@ -662,17 +708,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
     }
     block_sum<2>(kl, scratch, red);
     __syncthreads();
-    if (tid == 0) {
-        const int r = blockIdx.x % GPI_REPLICAS;
-        if (T.enc) {
-            if (d.flags & GPI_HEAD_REPARAM) atomicAdd(d.terms + 0 * GPI_REPLICAS + r, -0.5 * (double)red[0]);
-        } else {
-            // segments present in the tile, with their q_z KL
-            const int qa = T.s0 - d.n_enc, qb = qa + T.n;
-            if (qa < d.n_q && (d.flags & GPI_HEAD_QZ)) atomicAdd(d.terms + GPI_REPLICAS + r, -0.5 * (double)red[0]);
-            if (qb > d.n_q && (d.flags2 & GPI_HEAD_QZ)) atomicAdd(d.terms2 + r, -0.5 * (double)red[1]);
-        }
-    }
+    publish_kl(d, T, red);
     // decoder latent map (all samples) -> workspace
     if (d.flags & GPI_HEAD_LATENT) {
         const int dl = d.d_lat;
@@ -717,30 +753,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
         }
         const int64_t pi = (int64_t)sg.row * dx + t;           // q_X parameter row
         const float lsq = P[sg.qx_ls + pi];
-        const float xs = fmaf(expf(lsq), ws[d.eps_x + qi], P[sg.qx_mu + pi]);
+        const GpElemFwd E(P[sg.qx_mu + pi], lsq, ws[d.eps_x + qi]);
         ws[d.mux + qi] = a;
-        ws[d.xs + qi] = xs;
-        const float gls = P[d.gp_ls + t];
-        const float rr = xs - a;
+        ws[d.xs + qi] = E.xs;
         const int h = q >= d.n_q ? 2 : 0;
-        acc4[h] += -0.5f * (2.f * gls + rr * rr * expf(-2.f * gls) + GPI_LOG2PI);
+        acc4[h] += E.loglik(a, P[d.gp_ls + t]);
         acc4[h + 1] += lsq;
     }
     if ((gp1 && (d.flags & GPI_HEAD_LOCKX)) && (!gp2 || (d.flags2 & GPI_HEAD_LOCKX))) return;   // uniform
     block_sum<4>(acc4, scratch, red);
     __syncthreads();
-    if (tid == 0) {
-        const int r = blockIdx.x % GPI_REPLICAS;
-        const int qa = T.s0 - d.n_enc, qb = qa + T.n;
-        if (qa < d.n_q && gp1 && !(d.flags & GPI_HEAD_LOCKX)) {
-            atomicAdd(d.terms + 2 * GPI_REPLICAS + r, (double)red[0]);
-            atomicAdd(d.terms + 3 * GPI_REPLICAS + r, (double)red[1]);
-        }
-        if (qb > d.n_q && gp2 && !(d.flags2 & GPI_HEAD_LOCKX)) {
-            atomicAdd(d.terms2 + 1 * GPI_REPLICAS + r, (double)red[2]);
-            atomicAdd(d.terms2 + 2 * GPI_REPLICAS + r, (double)red[3]);
-        }
-    }
+    publish_lx(d, tile_has_seg(d, T, 0) && gp1 && !(d.flags & GPI_HEAD_LOCKX),
+               tile_has_seg(d, T, 1) && gp2 && !(d.flags2 & GPI_HEAD_LOCKX), red);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void head_bwd_mfma(gpi_head_desc d, const float* __restrict__ P, float* ws,
@@ -750,11 +774,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
     const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
     const HTile T = head_tile(d, blockIdx.x + t_off);
     const int dz = d.d_z, df = d.d_feat, dl = d.d_lat, dx = d.d_x;
-    zero_lds(sG, TS * LPW);
-    zero_lds(sGM, TS * LPW);
-    zero_lds(sDZ, TS * LPZ);
-    zero_lds(sDMU, TS * LPZ);
-    zero_lds(sDLS, TS * LPZ);
+    zero_lds<256>(sG, TS * LPW);
+    zero_lds<256>(sGM, TS * LPW);
+    zero_lds<256>(sDZ, TS * LPZ);
+    zero_lds<256>(sDMU, TS * LPZ);
+    zero_lds<256>(sDLS, TS * LPZ);
     __syncthreads();
     const bool lat = (d.flags & GPI_HEAD_LATENT) != 0;
     if (lat) rows_to_lds(ws + d.glat, T.s0, T.n, dl, sG, LPW);
@@ -780,18 +804,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
                 }
                 const int64_t pi = (int64_t)sg.row * dx + t;
                 const float gls = P[d.gp_ls + t];
-                const float e2 = expf(-2.f * gls);
-                const float xs = ws[d.xs + qi], mux = ws[d.mux + qi];
-                const float r = xs - mux;
-                const float gm = -sg.lx_scale * r * e2;         // dJ/dmu_X
+                const GpElemBwd G(ws[d.xs + qi], ws[d.mux + qi], gls, sg.lx_scale);
+                const float gm = G.gmux();
                 sGM[si * LPW + t] = gm;
                 ws[d.gmux + qi] = gm;
-                gls_sum += (double)(sg.lx_scale * (1.f - r * r * e2));
+                gls_sum += (double)G.gls();
                 any = true;
-                const float dxs = ws[d.gxs + qi] + sg.lx_scale * r * e2;   // dJ/dX~
+                const float dxs = G.gqx_mu(ws[d.gxs + qi]);
                 const float lsq = P[sg.qx_ls + pi];
                 gacc[sg.qx_mu + pi] += (double)dxs;
-                gacc[sg.qx_ls + pi] += (double)(dxs * expf(lsq) * ws[d.eps_x + qi] - sg.lx_scale);
+                gacc[sg.qx_ls + pi] += (double)G.gqx_ls(dxs, lsq, ws[d.eps_x + qi]);
             }
             if (any) atomicAdd(gacc + d.gp_ls + t, gls_sum);
         }
@@ -824,10 +846,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
             if (!(sg.flags & GPI_HEAD_QZ)) continue;
             const int64_t qi = (int64_t)sg.row * dz + k;
             const float mu = P[sg.qz_mu + qi], ls = P[sg.qz_ls + qi];
-            const float ex = expf(ls);
+            const ZDrawBwd G(ls, sg.kl_scale);
             const float dzv = sDZ[si * LPZ + k];
-            gacc[sg.qz_mu + qi] += (double)(dzv + sg.kl_scale * mu);
-            gacc[sg.qz_ls + qi] += (double)(dzv * ex * ws[d.eps_z + (int64_t)s * dz + k] + sg.kl_scale * (ex * ex - 1.f));
+            gacc[sg.qz_mu + qi] += (double)G.dmu(dzv, mu);
+            gacc[sg.qz_ls + qi] += (double)G.dls(dzv, ws[d.eps_z + (int64_t)s * dz + k]);
         }
         return;
     }
@@ -838,9 +860,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
         float dmu = sDZ[si * LPZ + k], dls;
         const float mu = ws[d.zmu + o], ls = ws[d.zls + o];
         if (d.flags & GPI_HEAD_REPARAM) {
-            const float ex = expf(ls);
-            dls = sDZ[si * LPZ + k] * ex * ws[d.eps_z + o] + d.kl_scale_enc * (ex * ex - 1.f);
-            dmu += d.kl_scale_enc * mu;
+            const ZDrawBwd G(ls, d.kl_scale_enc);
+            dls = G.dls(sDZ[si * LPZ + k], ws[d.eps_z + o]);
+            dmu = G.dmu(dmu, mu);
         } else {
             dls = ws[d.dzls + o];   // caller-provided d/dlogsigma
         }
@@ -883,14 +905,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void hea
 // gacc[c_off + m N + n] += sum_s A[s][m] B[s][n] for one 16 x 16 output tile (column N: the bias, B = 1):
 // the samples split over the four waves in contiguous quarters (4 samples per MFMA, every operand load of
 // a 64-sample group in flight at once), the waves' partial tiles summed in LDS in wave order.
-struct GemmArgsM {
-    gpi_gemm_item it[GPI_MAX_GEMM_ITEMS];
-    int32_t first_block[GPI_MAX_GEMM_ITEMS + 1];
-    int32_t tiles_n[GPI_MAX_GEMM_ITEMS];
-    int32_t n;
-};
-
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void outer_gemm_mfma(GemmArgsM a, const float* __restrict__ ws, double* gacc) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void outer_gemm_mfma(GemmArgs a, const float* __restrict__ ws, double* gacc) {
     __shared__ float part[4][16][17];
     int k = 0;
     while (k + 1 < a.n && (int)blockIdx.x >= a.first_block[k + 1]) ++k;
@@ -953,26 +968,11 @@ struct Ops {
     hf32x4 a[NC];
 };
 
-// A operands of output block jb (< 0: zeros) of a J x K product, K <= 16 NC (16-wide chunks, lane (i, g):
-// rows 16 jb + i, k = 16 c + 4 g + t): WT = false reads W[j K + k] (float4), WT = true W[k J + j]
+// A operands (aload) of output block jb (< 0: zeros) of a J x K product, K <= 16 NC: all NC chunks
 template <bool WT, int NC>
 __device__ __forceinline__ void wload(const float* __restrict__ W, int J, int K, int jb, Ops<NC>& o) {
-    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
-    const int j = 16 * jb + i;
-    const bool jok = jb >= 0 && j < J;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int k = 16 * c + 4 * g;
-        o.a[c] = hf32x4{0.f, 0.f, 0.f, 0.f};
-        if (jok && k < K) {
-            if constexpr (!WT) {
-                o.a[c] = *reinterpret_cast<const hf32x4*>(W + (j * K + k));
-            } else {
-                const int q = k * J + j;
-                o.a[c] = hf32x4{W[q], W[q + J], W[q + 2 * J], W[q + 3 * J]};
-            }
-        }
-    }
+    for (int c = 0; c < NC; ++c) o.a[c] = aload<WT>(W, J, K, jb, 16 * c);
 }
 
 template <int NC>
@@ -995,10 +995,6 @@ __device__ __forceinline__ hf32x4 bload(const float* __restrict__ b, int J, int 
     hf32x4 v{0.f, 0.f, 0.f, 0.f};
     if (jb >= 0 && j < J) v = hf32x4{b[j], b[j + 1], b[j + 2], b[j + 3]};
     return v;
-}
-
-__device__ __forceinline__ void zero_lds2(float* p, int n) {   // 512 threads
-    for (int e = threadIdx.x; e < n / 4; e += HT2) reinterpret_cast<float4*>(p)[e] = float4{0.f, 0.f, 0.f, 0.f};
 }
 
 template <int CF, int CZ, int CL, int CX>
@@ -1094,10 +1090,10 @@ __global__ __launch_bounds__(HT2) __attribute__((amdgpu_num_vgpr(128))) void hea
         xE[u] = ws[d.eps_x + (int64_t)(qa + si) * DX + t];
         xG[u] = P[d.gp_ls + t];
     }
-    zero_lds2(sX, TS * PF);
-    zero_lds2(sH, TS * PF);
-    zero_lds2(sZ, TS * PZ);
-    zero_lds2(sG, TS * PX);
+    zero_lds<HT2>(sX, TS * PF);
+    zero_lds<HT2>(sH, TS * PF);
+    zero_lds<HT2>(sZ, TS * PZ);
+    zero_lds<HT2>(sG, TS * PX);
     __syncthreads();
     if (enc_fc) {
 #pragma unroll
@@ -1150,24 +1146,16 @@ __global__ __launch_bounds__(HT2) __attribute__((amdgpu_num_vgpr(128))) void hea
             h = qa + si >= d.n_q;
         }
         if (draw) {
-            const float ex = expf(ls);
-            zz = fmaf(ex, eE[u], mu);
+            const ZDraw D(mu, ls);
+            zz = D.z(eE[u]);
             ws[d.z + o] = zz;
-            kl[h] += 1.f + 2.f * ls - mu * mu - ex * ex;
+            kl[h] += D.kl();
         }
         sZ[si * PZ + k] = zz;
     }
     block_sum<2>(kl, scratch, red);
     __syncthreads();
-    if (tid == 0) {
-        const int r = blockIdx.x % GPI_REPLICAS;
-        if (T.enc) {
-            if (reparam) atomicAdd(d.terms + r, -0.5 * (double)red[0]);
-        } else {
-            if (qa < d.n_q && (d.flags & GPI_HEAD_QZ)) atomicAdd(d.terms + GPI_REPLICAS + r, -0.5 * (double)red[0]);
-            if (qa + T.n > d.n_q && (d.flags2 & GPI_HEAD_QZ)) atomicAdd(d.terms2 + r, -0.5 * (double)red[1]);
-        }
-    }
+    publish_kl(d, T, red);
     // decoder latent map -> workspace; effective-property map gp(z) -> sG
     if (lat && w < CL) {
         const hf32x4 a = wmma(aL, sZ, PZ, hf32x4{0.f, 0.f, 0.f, 0.f}) + bL;
@@ -1194,30 +1182,18 @@ __global__ __launch_bounds__(HT2) __attribute__((amdgpu_num_vgpr(128))) void hea
             ws[d.xs + qi] = a;
             continue;
         }
-        const float xs = fmaf(expf(xL[u]), xE[u], xM[u]);
+        const GpElemFwd E(xM[u], xL[u], xE[u]);
         ws[d.mux + qi] = a;
-        ws[d.xs + qi] = xs;
-        const float gls = xG[u];
-        const float rr = xs - a;
+        ws[d.xs + qi] = E.xs;
         const int h = q >= d.n_q ? 2 : 0;
-        acc4[h] += -0.5f * (2.f * gls + rr * rr * expf(-2.f * gls) + GPI_LOG2PI);
+        acc4[h] += E.loglik(a, xG[u]);
         acc4[h + 1] += xL[u];
     }
     const bool lx1 = gp1 && !(d.flags & GPI_HEAD_LOCKX), lx2 = gp2 && !(d.flags2 & GPI_HEAD_LOCKX);
     if (!lx1 && !lx2) return;   // uniform
     block_sum<4>(acc4, scratch, red);
     __syncthreads();
-    if (tid == 0) {
-        const int r = blockIdx.x % GPI_REPLICAS;
-        if (lx1) {
-            atomicAdd(d.terms + 2 * GPI_REPLICAS + r, (double)red[0]);
-            atomicAdd(d.terms + 3 * GPI_REPLICAS + r, (double)red[1]);
-        }
-        if (lx2) {
-            atomicAdd(d.terms2 + 1 * GPI_REPLICAS + r, (double)red[2]);
-            atomicAdd(d.terms2 + 2 * GPI_REPLICAS + r, (double)red[3]);
-        }
-    }
+    publish_lx(d, lx1, lx2, red);
 }
 
 template <int CF, int CZ, int CL, int CX>
@@ -1304,12 +1280,12 @@ __global__ __launch_bounds__(HT2) __attribute__((amdgpu_num_vgpr(128))) void hea
         xL[u] = P[sg.qx_ls + (int64_t)sg.row * DX + t];
         xG[u] = P[d.gp_ls + t];
     }
-    zero_lds2(sG, TS * PL);
-    zero_lds2(sGM, TS * PX);
-    zero_lds2(sC, TS * PX);
-    zero_lds2(sDMU, TS * PZ);
-    zero_lds2(sDLS, TS * PZ);
-    zero_lds2(sDH, TS * PF);
+    zero_lds<HT2>(sG, TS * PL);
+    zero_lds<HT2>(sGM, TS * PX);
+    zero_lds<HT2>(sC, TS * PX);
+    zero_lds<HT2>(sDMU, TS * PZ);
+    zero_lds<HT2>(sDLS, TS * PZ);
+    zero_lds<HT2>(sDH, TS * PF);
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < LU; ++u) {
@@ -1331,17 +1307,16 @@ __global__ __launch_bounds__(HT2) __attribute__((amdgpu_num_vgpr(128))) void hea
             continue;
         }
         const int64_t pi = (int64_t)sg.row * DX + t;
-        const float e2 = expf(-2.f * xG[u]);
-        const float r = xS[u] - xMu[u];
-        const float gm = -sg.lx_scale * r * e2;              // dJ/dmu_X
+        const GpElemBwd G(xS[u], xMu[u], xG[u], sg.lx_scale);
+        const float gm = G.gmux();
         sGM[si * PX + t] = gm;
         ws[d.gmux + qi] = gm;
-        sC[si * PX + t] = sg.lx_scale * (1.f - r * r * e2);
-        const float dxs = xGx[u] + sg.lx_scale * r * e2;     // dJ/dX~
+        sC[si * PX + t] = G.gls();
+        const float dxs = G.gqx_mu(xGx[u]);
         // (per-sample rows, one writer each: the atomic is a fire-and-forget read-modify-write, no load round
         // trip inside the kernel)
         atomicAdd(gacc + sg.qx_mu + pi, (double)dxs);
-        atomicAdd(gacc + sg.qx_ls + pi, (double)(dxs * expf(xL[u]) * xE[u] - sg.lx_scale));
+        atomicAdd(gacc + sg.qx_ls + pi, (double)G.gqx_ls(dxs, xL[u], xE[u]));
     }
     __syncthreads();
     if (lat && w < CZ) {
@@ -1378,9 +1353,9 @@ __global__ __launch_bounds__(HT2) __attribute__((amdgpu_num_vgpr(128))) void hea
             const QSeg sg = qseg(d, qa + si);
             if (!(sg.flags & GPI_HEAD_QZ)) continue;
             const int64_t qi = (int64_t)sg.row * DZ + k;
-            const float ex = expf(eL[u]);
-            atomicAdd(gacc + sg.qz_mu + qi, (double)(dzv[u] + sg.kl_scale * eM[u]));
-            atomicAdd(gacc + sg.qz_ls + qi, (double)(dzv[u] * ex * eE[u] + sg.kl_scale * (ex * ex - 1.f)));
+            const ZDrawBwd G(eL[u], sg.kl_scale);
+            atomicAdd(gacc + sg.qz_mu + qi, (double)G.dmu(dzv[u], eM[u]));
+            atomicAdd(gacc + sg.qz_ls + qi, (double)G.dls(dzv[u], eE[u]));
         }
         return;
     }
@@ -1392,9 +1367,9 @@ __global__ __launch_bounds__(HT2) __attribute__((amdgpu_num_vgpr(128))) void hea
         const int64_t o = (int64_t)(T.s0 + si) * DZ + k;
         float dmu = dzv[u], dls;
         if (d.flags & GPI_HEAD_REPARAM) {
-            const float ex = expf(eL[u]);
-            dls = dzv[u] * ex * eE[u] + d.kl_scale_enc * (ex * ex - 1.f);
-            dmu += d.kl_scale_enc * eM[u];
+            const ZDrawBwd G(eL[u], d.kl_scale_enc);
+            dls = G.dls(dzv[u], eE[u]);
+            dmu = G.dmu(dmu, eM[u]);
         } else {
             dls = eE[u];
         }
@@ -1423,13 +1398,35 @@ __global__ __launch_bounds__(HT2) __attribute__((amdgpu_num_vgpr(128))) void hea
     }
 }
 
-// the prefetched form's widths (0: none): d_feat / d_z / d_lat / d_x = 16 x (CF, CZ, CL, CX)
+// the prefetched form's width families, d_feat / d_z / d_lat / d_x = 16 x (cf, cz, cl, cx): highres, highres32.
+// head_family and launch_mfma2 read this table alone: a further family is one more entry.
+struct Family {
+    int cf, cz, cl, cx;
+};
+constexpr Family FAMILIES[] = {{5, 4, 4, 8}, {4, 1, 4, 2}};
+constexpr int N_FAMILIES = sizeof(FAMILIES) / sizeof(FAMILIES[0]);
+
+// 1 + the index of the descriptor's family (0: none); d_feat counts only where the encoder FC runs
 int head_family(const gpi_head_desc* d) {
     const bool enc = (d->flags & GPI_HEAD_ENC) && d->n_enc > 0;
-    const int df = enc ? d->d_feat : 0;
-    if ((df == 80 || !enc) && d->d_z == 64 && d->d_lat == 64 && d->d_x == 128) return 1;
-    if ((df == 64 || !enc) && d->d_z == 16 && d->d_lat == 64 && d->d_x == 32) return 2;
+    for (int f = 0; f < N_FAMILIES; ++f) {
+        const Family& F = FAMILIES[f];
+        if ((!enc || d->d_feat == 16 * F.cf) && d->d_z == 16 * F.cz && d->d_lat == 16 * F.cl && d->d_x == 16 * F.cx)
+            return 1 + f;
+    }
     return 0;
+}
+
+// family fam's instantiation of the prefetched kernels over nt tiles: the backward with gacc, else the forward
+template <int F = 0>
+void launch_mfma2(int fam, int nt, hipStream_t st, const gpi_head_desc& d, const float* P, float* ws, double* gacc,
+                  int t_off) {
+    if constexpr (F < N_FAMILIES) {
+        if (fam != 1 + F) return launch_mfma2<F + 1>(fam, nt, st, d, P, ws, gacc, t_off);
+        constexpr Family C = FAMILIES[F];
+        if (gacc) hipLaunchKernelGGL((head_bwd_mfma2<C.cf, C.cz, C.cl, C.cx>), dim3(nt), dim3(HT2), 0, st, d, P, ws, gacc, t_off);
+        else hipLaunchKernelGGL((head_fwd_mfma2<C.cf, C.cz, C.cl, C.cx>), dim3(nt), dim3(HT2), 0, st, d, P, ws);
+    }
 }
 
 // the MFMA kernels' preconditions: widths that fit the LDS row buffers, float4-aligned rows
@@ -1448,12 +1445,28 @@ bool head_mfma_gate(const gpi_head_desc* d) {
     return true;
 }
 
-bool head_mfma_ok(const gpi_head_desc* d) {
-    static const int on = [] {
-        const char* v = getenv("GPI_HEAD_MFMA");
-        return v && *v ? atoi(v) : 1;
-    }();
-    return on && head_mfma_gate(d);
+int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
+}
+
+// GPI_HEAD_MFMA (default 1), read once per process: 0 sends every head and GEMM launch to the VALU kernels
+bool mfma_enabled() {
+    static const int on = env_int("GPI_HEAD_MFMA", 1);
+    return on != 0;
+}
+
+// The kernel form of a descriptor, the value gpi_head_form reports: 0 the per-sample VALU kernels, 1 the generic
+// MFMA form, 1 + family the prefetched form.
+int head_form(const gpi_head_desc* d, bool mfma, bool prefetch) {
+    if (!mfma || !head_mfma_gate(d)) return 0;
+    return 1 + (prefetch ? head_family(d) : 0);
+}
+
+// the form a launch takes: head_form under GPI_HEAD_MFMA and GPI_HEAD_PREFETCH (default 1, read once per process)
+int launch_form(const gpi_head_desc* d) {
+    static const int pf = env_int("GPI_HEAD_PREFETCH", 1);
+    return head_form(d, mfma_enabled(), pf != 0);
 }
 
 bool head_ok(const gpi_head_desc* d) {
@@ -1466,31 +1479,17 @@ bool head_ok(const gpi_head_desc* d) {
 
 extern "C" int gpi_head_form(const gpi_head_desc* d, int prefetch) {
     if (!head_ok(d)) return GPI_ERR_ARG;
-    if (!head_mfma_gate(d)) return 0;
-    const int fam = prefetch ? head_family(d) : 0;
-    return fam ? 1 + fam : 1;
+    return head_form(d, true, prefetch != 0);
 }
 
 extern "C" int gpi_head_forward(const gpi_head_desc* d, const float* params, float* ws, void* stream) {
     if (!head_ok(d) || !params || !ws) return GPI_ERR_ARG;
-    if (head_mfma_ok(d)) {
-        const int nt = (d->n_enc + TS - 1) / TS + (d->n_q + d->n_q2 + TS - 1) / TS;
-        static const int pf = [] {
-            const char* v = getenv("GPI_HEAD_PREFETCH");
-            return v && *v ? atoi(v) : 1;
-        }();
-        const int fam = pf ? head_family(d) : 0;
-        if (fam) {
-            if (fam == 1) hipLaunchKernelGGL((head_fwd_mfma2<5, 4, 4, 8>), dim3(nt), dim3(HT2), 0, (hipStream_t)stream, *d, params, ws);
-            else hipLaunchKernelGGL((head_fwd_mfma2<4, 1, 4, 2>), dim3(nt), dim3(HT2), 0, (hipStream_t)stream, *d, params, ws);
-            GPI_CHECK_LAUNCH();
-            return GPI_OK;
-        }
-        hipLaunchKernelGGL(head_fwd_mfma, dim3(nt), dim3(256), 0, (hipStream_t)stream, *d, params, ws);
-        GPI_CHECK_LAUNCH();
-        return GPI_OK;
-    }
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(d->n_enc + d->n_q + d->n_q2), dim3(HT), 0, (hipStream_t)stream, *d, params, ws);
+    const hipStream_t st = (hipStream_t)stream;
+    const int form = launch_form(d);
+    const int nt = (d->n_enc + TS - 1) / TS + (d->n_q + d->n_q2 + TS - 1) / TS;
+    if (form > 1) launch_mfma2(form - 1, nt, st, *d, params, ws, nullptr, 0);
+    else if (form == 1) hipLaunchKernelGGL(head_fwd_mfma, dim3(nt), dim3(256), 0, st, *d, params, ws);
+    else hipLaunchKernelGGL(head_fwd_kernel, dim3(d->n_enc + d->n_q + d->n_q2), dim3(HT), 0, st, *d, params, ws);
     GPI_CHECK_LAUNCH();
     return GPI_OK;
 }
@@ -1503,29 +1502,13 @@ extern "C" int gpi_head_backward(const gpi_head_desc* d, const float* params, fl
     const int nq = d->n_q + d->n_q2;
     const int nb = pe ? d->n_enc : (pq ? nq : d->n_enc + nq), s_off = pq ? d->n_enc : 0;
     if (nb == 0) return GPI_OK;
-    if (head_mfma_ok(d)) {
-        const int et = (d->n_enc + TS - 1) / TS, qt = (nq + TS - 1) / TS;
-        const int ntl = pe ? et : (pq ? qt : et + qt), t_off = pq ? et : 0;
-        static const int pf = [] {
-            const char* v = getenv("GPI_HEAD_PREFETCH");
-            return v && *v ? atoi(v) : 1;
-        }();
-        const int fam = pf ? head_family(d) : 0;
-        if (fam) {
-            if (fam == 1)
-                hipLaunchKernelGGL((head_bwd_mfma2<5, 4, 4, 8>), dim3(ntl), dim3(HT2), 0, (hipStream_t)stream, *d, params, ws,
-                                   gacc, t_off);
-            else
-                hipLaunchKernelGGL((head_bwd_mfma2<4, 1, 4, 2>), dim3(ntl), dim3(HT2), 0, (hipStream_t)stream, *d, params, ws,
-                                   gacc, t_off);
-            GPI_CHECK_LAUNCH();
-            return GPI_OK;
-        }
-        hipLaunchKernelGGL(head_bwd_mfma, dim3(ntl), dim3(256), 0, (hipStream_t)stream, *d, params, ws, gacc, t_off);
-        GPI_CHECK_LAUNCH();
-        return GPI_OK;
-    }
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(nb), dim3(HT), 0, (hipStream_t)stream, *d, params, ws, gacc, s_off);
+    const hipStream_t st = (hipStream_t)stream;
+    const int form = launch_form(d);
+    const int et = (d->n_enc + TS - 1) / TS, qt = (nq + TS - 1) / TS;
+    const int ntl = pe ? et : (pq ? qt : et + qt), t_off = pq ? et : 0;
+    if (form > 1) launch_mfma2(form - 1, ntl, st, *d, params, ws, gacc, t_off);
+    else if (form == 1) hipLaunchKernelGGL(head_bwd_mfma, dim3(ntl), dim3(256), 0, st, *d, params, ws, gacc, t_off);
+    else hipLaunchKernelGGL(head_bwd_kernel, dim3(nb), dim3(HT), 0, st, *d, params, ws, gacc, s_off);
     GPI_CHECK_LAUNCH();
     return GPI_OK;
 }
@@ -1545,24 +1528,11 @@ extern "C" int gpi_outer_gemm(const gpi_gemm_item* items, int n_items, const flo
         nb += tm * tn;
     }
     a.first_block[n_items] = nb;
-    static const int mf = [] {
-        const char* v = getenv("GPI_HEAD_MFMA");
-        return v && *v ? atoi(v) : 1;
-    }();
-    if (mf && !(items[0].flags & 2)) {
-        GemmArgsM am;
-        am.n = a.n;
-        for (int k = 0; k < n_items; ++k) {
-            am.it[k] = a.it[k];
-            am.first_block[k] = a.first_block[k];
-            am.tiles_n[k] = a.tiles_n[k];
-        }
-        am.first_block[n_items] = nb;
-        hipLaunchKernelGGL(outer_gemm_mfma, dim3(nb), dim3(256), 0, (hipStream_t)stream, am, ws, gacc);
-        GPI_CHECK_LAUNCH();
-        return GPI_OK;
-    }
-    hipLaunchKernelGGL(outer_gemm_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, ws, gacc);
+    if (mfma_enabled() && !(items[0].flags & 2))
+        hipLaunchKernelGGL(outer_gemm_mfma, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, ws, gacc);
+    else
+        hipLaunchKernelGGL(outer_gemm_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, ws, gacc);
     GPI_CHECK_LAUNCH();
     return GPI_OK;
 }
+

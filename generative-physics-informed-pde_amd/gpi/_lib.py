@@ -335,13 +335,13 @@ INCLUDE_H = os.path.join(os.path.dirname(os.path.dirname(HERE)), 'include', 'gpi
 
 def source_sha():
     """sha1 of the library's sources as csrc/Makefile computes it (csrc/*.hip in name order, csrc/common.h,
-    csrc/conv_shapes.h, csrc/vo_grid.h, include/gpi.h, concatenated); None when the sources are not next to the
-    package."""
+    csrc/conv_shapes.h, csrc/dense_terms.h, csrc/vo_grid.h, include/gpi.h, concatenated); None when the sources are
+    not next to the package."""
     import glob
     import hashlib
     files = sorted(glob.glob(os.path.join(SRC_DIR, '*.hip')), key=os.path.basename)
     files += [os.path.join(SRC_DIR, 'common.h'), os.path.join(SRC_DIR, 'conv_shapes.h'),
-              os.path.join(SRC_DIR, 'vo_grid.h'), INCLUDE_H]
+              os.path.join(SRC_DIR, 'dense_terms.h'), os.path.join(SRC_DIR, 'vo_grid.h'), INCLUDE_H]
     if not all(os.path.exists(f) for f in files):
         return None
     h = hashlib.sha1()

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib as L
 from .plan import Arena, encoder_program, decoder_program
+from .schedule import MAIN, SIDE, E_ROM, E_DEC, E_ENC, E_SIDE, E_VALUE, step_schedule, walk
 
 ENT_CONST = 0.5 * (math.log(2 * math.pi) + 1)
 N_TERMS = 16
@@ -124,8 +125,117 @@ def make_ctx(ws, flat, group_sizes):
     return c
 
 
+HEAD_PARAMS = ('fc_w', 'fc_b', 'mu_w', 'mu_b', 'ls_w', 'ls_b', 'lat_w', 'lat_b', 'gp_w', 'gp_b', 'gp_ls', 'qz_mu',
+               'qz_ls', 'qx_mu', 'qx_ls')
+HEAD_PARAMS2 = ('qz_mu2', 'qz_ls2', 'qx_mu2', 'qx_ls2')
+HEAD_BUFFERS = ('hpre', 'dhpre', 'zmu', 'zls', 'eps_z', 'z', 'gz', 'dzmu', 'dzls', 'eps_x', 'xs', 'mux', 'gxs', 'gmux')
+ENC_HEAD = dict(fc_w='features.FC.weight', fc_b='features.FC.bias', mu_w='features.SplitDense.fc_mean.weight',
+                mu_b='features.SplitDense.fc_mean.bias', ls_w='features.SplitDense.fc_logvar.weight',
+                ls_b='features.SplitDense.fc_logvar.bias')
+DEC_HEAD = dict(lat_w='latent_map.weight', lat_b='latent_map.bias')
+
+
+def head_desc(hb, ws, second=False, **fields):
+    """The HeadDesc builder of every engine: each parameter offset -1, each scale 1.0, the workspace buffers of hb,
+    the term slots; a caller sets only what it uses (fields).  second: the second variational segment's offsets,
+    scales and term slots too (ElboEngine); the codec engines have none (flags2 = 0: its fields are never read,
+    and stay zero)."""
+    h = L.HeadDesc()
+    for k in HEAD_PARAMS + (HEAD_PARAMS2 if second else ()):
+        setattr(h, k, -1)
+    for k in ('kl_scale_enc', 'kl_scale_q', 'lx_scale') + (('kl_scale_q2', 'lx_scale2') if second else ()):
+        setattr(h, k, 1.0)
+    for k, v in hb.items():
+        setattr(h, k, v)
+    h.terms = ws.term_ptr(T_KL_ENC).value
+    if second:
+        h.terms2 = ws.term_ptr(T_KL_Q2).value
+    for k, v in fields.items():
+        setattr(h, k, v)
+    return h
+
+
+def codec_head_buffers(ws, B, dz, d_feat=0):
+    """Head buffers of a standalone codec engine (the allocation order is the layout): the encoder's with
+    hpre / dhpre [B, d_feat] first; the buffers it does not use at offset 0."""
+    sizes = ([('hpre', d_feat), ('dhpre', d_feat)] if d_feat else []) + \
+        [(k, dz) for k in ('zmu', 'zls', 'eps_z', 'z', 'gz', 'dzmu', 'dzls')]
+    hb = {k: ws.alloc(B * n) for k, n in sizes}
+    hb.update({k: 0 for k in HEAD_BUFFERS if k not in hb})
+    return hb
+
+
+def encoder_head(p, hb, ws, off, B, dz, train=True):
+    """HeadDesc of a standalone encoder (program p): conv features -> (mean, logsigma)."""
+    return head_desc(hb, ws, flags=L.HEAD_ENC, n_enc=B, n_q=0, d_feat=p.d_feat, d_z=dz, d_lat=1, d_x=1,
+                     feat=p.output.off, gfeat=p.output.s_off if train else 0,
+                     **{k: off(n) for k, n in ENC_HEAD.items()})
+
+
+def decoder_head(p, hb, ws, off, B, dz, train=True):
+    """HeadDesc of a standalone decoder (program p): the latent map z -> the first conv's input."""
+    return head_desc(hb, ws, flags=L.HEAD_LATENT, n_enc=B, n_q=0, d_feat=1, d_z=dz, d_lat=p.input.per_sample, d_x=1,
+                     lat=p.input.off, glat=p.input.s_off if train else 0, **{k: off(n) for k, n in DEC_HEAD.items()})
+
+
+def gemm_item(a, b, S, M, N, lda, ldb, c, bias, flags=0):
+    return L.GemmItem(a_off=a, b_off=b, c_off=c, bias_off=bias, S=S, M=M, N=N, lda=lda, ldb=ldb, flags=flags)
+
+
+def encoder_head_gemms(h, hb, n):
+    """Weight-gradient items of the encoder head's three Linear layers over its n samples."""
+    dz, df = h.d_z, h.d_feat
+    return [gemm_item(hb['dzmu'], hb['hpre'], n, dz, df, dz, df, h.mu_w, h.mu_b, 1),
+            gemm_item(hb['dzls'], hb['hpre'], n, dz, df, dz, df, h.ls_w, h.ls_b, 1),
+            gemm_item(hb['dhpre'], h.feat, n, df, df, df, df, h.fc_w, h.fc_b)]
+
+
+def decoder_latent_gemms(h, hb, n):
+    """Weight-gradient item of the decoder's latent map over its n samples."""
+    return [gemm_item(h.glat, hb['z'], n, h.d_lat, h.d_z, h.d_lat, h.d_z, h.lat_w, h.lat_b)]
+
+
+def gemm_array(items):
+    return (L.GemmItem * len(items))(*items)
+
+
+def codec_setup(e, kind, module, flat, B, train=True):
+    """What the standalone codec engines (train and eval, 'enc' and 'dec') share, as attributes of e: the program
+    p and its layout descs, the head buffers hb, the materialised workspace ws, the head descriptor and the codec
+    context ctx.  Returns the module's parameter-offset function."""
+    e.flat, e.B = flat, int(B)
+    ws = e.ws = Workspace()
+    off = lambda n: flat.offset(module.get_parameter(n))
+    cfg = module.native_config()
+    e.p = encoder_program(**cfg) if kind == 'enc' else decoder_program(final_epilogue=None, **cfg)
+    e.descs = e.p.layout(e.B, ws.ws, ws.stats, ws.parts, groups_struct([e.B]), off, eval_mode=not train)
+    e.dz = module.latent_dim if kind == 'enc' else module.dim_latent
+    e.hb = codec_head_buffers(ws, e.B, e.dz, e.p.d_feat if kind == 'enc' else 0)
+    ws.materialize(flat.P.device)
+    e.head = (encoder_head if kind == 'enc' else decoder_head)(e.p, e.hb, ws, off, e.B, e.dz, train)
+    e.ctx = make_ctx(ws, flat, [e.B])
+    if kind == 'enc':
+        e.ctx.ext_stride = e.p.input.per_sample
+    return off
+
+
 def _lib():
     return L.lib()
+
+
+def head_forward(h, flat, ws, st, what='head forward'):
+    _run(_lib().gpi_head_forward, C.byref(h), C.c_void_p(flat.P.data_ptr()), C.c_void_p(ws.t_ws.data_ptr()), st,
+         what=what)
+
+
+def head_backward(h, flat, ws, st, what='head backward'):
+    _run(_lib().gpi_head_backward, C.byref(h), C.c_void_p(flat.P.data_ptr()), C.c_void_p(ws.t_ws.data_ptr()),
+         C.c_void_p(flat.gacc.data_ptr()), st, what=what)
+
+
+def outer_gemm(items, flat, ws, st):
+    _run(_lib().gpi_outer_gemm, items, len(items), C.c_void_p(ws.t_ws.data_ptr()), C.c_void_p(flat.gacc.data_ptr()),
+         st, what='outer gemm')
 
 
 def run_reduce(items, ws, flat, st):
@@ -209,6 +319,72 @@ def inject_dropout(views, masks):
             views[key][name].copy_(m)
 
 
+class EventJoiner(object):
+    """The schedule's edges as events: record on the signalling stream, wait_event on the waiting one
+    (ElboEngine.handoff None).  streams: {MAIN / SIDE: (torch stream, launch handle)}."""
+
+    def __init__(self, events, streams):
+        self.ev, self.streams = events, streams
+
+    def begin(self):
+        pass
+
+    def signal(self, edge, stream, fold):
+        self.ev[edge].record(self.streams[stream][0])
+
+    def wait(self, edge, stream):
+        self.streams[stream][0].wait_event(self.ev[edge])
+
+    def end(self):
+        pass
+
+
+class FlagJoiner(object):
+    """Edges 0 .. 3 as device flags (gpi_stream_signal / gpi_stream_wait; ElboEngine.set_flag_handoff); a signal
+    the table marks fold rides on the next main-stream piece's first conv launch.  E_VALUE stays an event."""
+
+    def __init__(self, engine, events, main_wait):
+        self.e, self.events, self.streams, self.main_wait = engine, events, events.streams, main_wait
+
+    def begin(self):
+        # the side stream's one fork of the step, before any of its kernels: its flag waits then
+        # follow this step's signals only (never the previous step's); side_done: by the step counter
+        e = self.e
+        if e.side_done is not None:
+            _, epoch, err = e.handoff
+            _run(_lib().gpi_stream_wait_ge, C.c_void_p(epoch.data_ptr()), C.c_void_p(e.side_done.data_ptr()),
+                 C.c_void_p(err.data_ptr()) if err is not None else None, self.streams[SIDE][1],
+                 what='side step gate')
+        else:
+            self.events.signal('start', MAIN, False)
+            self.events.wait('start', SIDE)
+
+    def signal(self, edge, stream, fold):
+        if edge == E_VALUE:
+            return self.events.signal(edge, stream, fold)
+        if fold:
+            return edge
+        self.e._signal(edge, self.streams[stream][1])
+
+    def wait(self, edge, stream):
+        if edge == E_VALUE:
+            self.events.wait(edge, stream)
+        elif edge != E_SIDE or self.main_wait:
+            # (the side's end: a wait launch on the main chain, or folded into the caller's epilogue: main_wait False)
+            self.e._wait(edge, self.streams[stream][1])
+
+    def end(self):
+        # side_done: the side stream's step ends by incrementing the counter its next step gate reads; else the
+        # event join (capture legality) after the step's last kernel: rejoin()
+        e = self.e
+        if e.side_done is not None:
+            _run(_lib().gpi_rng_advance, C.c_void_p(e.side_done.data_ptr()), 1, self.streams[SIDE][1],
+                 what='side step done')
+        else:
+            self.events.signal(E_SIDE, SIDE, False)
+            e._rejoin_pending = True
+
+
 class ElboEngine(object):
     """Fused armortized-unsupervised + supervised-freeX (+ virtual-observable freeX) ELBO of a
     GenerativeModel.  N_vo > 0 adds the VO term (its own decoder BN group, q_z['vo'] / q_X['vo']
@@ -228,9 +404,7 @@ class ElboEngine(object):
         self.model = model
         self.q_unsup = q_unsup
         self.armortized = q_unsup is None
-        flat = model._flat
-        self.flat = flat
-        dev = flat.P.device
+        self.flat = model._flat
         self.B_u, self.N_s, self.N_vo = int(B_u), int(N_s), int(N_vo)
         self.vo_holdoff = bool(vo_holdoff) and self.N_vo > 0
         self.N_q = self.N_s + self.N_vo
@@ -242,22 +416,34 @@ class ElboEngine(object):
         # lockX (independent_X = False): X~ = gp(z), no q_X rows, no q_X noise, no logL_X / entropy
         self.lockx = not gp.independent_X
         self.N_ex = 0 if self.lockx else self.N_x
-        self.enc, self.dec = enc, dec
-        ws = Workspace()
-        self.ws = ws
-        offE = (lambda n: flat.offset(enc.get_parameter(n))) if enc is not None else None
-        offD = lambda n: flat.offset(dec.get_parameter(n))
-        dz = dec.dim_latent
-        self.dz = dz
+        self.enc, self.dec, self.gp, self.g = enc, dec, gp, g
+        self.dz = dec.dim_latent
+        self.ws = Workspace()
+        self._build_layout()
+        self._build_head()
+        self._build_gemm_items()
+        self._build_roms(y_weight)
+        self._build_switches(running_modules or {})
+
+    def _poff(self, mod, name):
+        return self.flat.offset(mod.get_parameter(name))
+
+    def _build_layout(self):
+        """Programs and workspace layout: ep / enc_descs, dp / dec_descs, n_enc_conv, n_dec_sep, the head
+        buffers hb, gp_mlp_buffers, gls_off, the materialised workspace and the codec contexts ectx / dctx.  The
+        order of the allocations is the layout: every workspace offset, and so every descriptor, follows it."""
+        model, flat, ws, dz = self.model, self.flat, self.ws, self.dz
+        enc, dec, gp, g = self.enc, self.dec, self.gp, self.g
         # ---- encoder program
         if self.B_u > 0 and self.armortized:
-            ec = enc.native_config()
-            self.ep = encoder_program(**ec)
-            self.enc_descs = self.ep.layout(self.B_u, ws.ws, ws.stats, ws.parts, groups_struct([self.B_u]), offE)
+            self.ep = encoder_program(**enc.native_config())
+            self.enc_descs = self.ep.layout(self.B_u, ws.ws, ws.stats, ws.parts, groups_struct([self.B_u]),
+                                            lambda n: self._poff(enc, n))
             d_feat = self.ep.d_feat
         else:
             self.ep = None
             d_feat = 1
+        self.d_feat = d_feat
         # ---- decoder program (groups: unsup, sup, vo)
         dc = dec.native_config()
         # the decoder likelihood of generative.py:232-244: log-property Gaussian (default) or the
@@ -271,8 +457,10 @@ class ElboEngine(object):
         self.dec_sizes = [n for n in (self.B_u, self.N_s, self.N_vo) if n > 0]
         self.g_sup = (1 if self.B_u > 0 else 0) if self.N_s > 0 else None
         self.g_vo = ((self.B_u > 0) + (self.N_s > 0)) if self.N_vo > 0 else None
-        self.dec_descs = self.dp.layout(self.B, ws.ws, ws.stats, ws.parts, groups_struct(self.dec_sizes), offD)
-        # codec launch ranges: the encoder's ops [0, n_enc_conv), the decoder's [dec0, ...)
+        self.dec_descs = self.dp.layout(self.B, ws.ws, ws.stats, ws.parts, groups_struct(self.dec_sizes),
+                                        lambda n: self._poff(dec, n))
+        # codec launch ranges: the encoder's ops [0, n_enc_conv), the decoder's [0, n_dec_sep) (+ the fused output
+        # conv); dec0 = 0 is read by bench.py's launch list only
         self.n_enc_conv = len(self.enc_descs) if self.ep is not None else 0
         self.dec0 = 0
         # the loss epilogue consumes (mu, logsigma) in registers: nobody reads the output image (9.4 MB of
@@ -285,13 +473,13 @@ class ElboEngine(object):
         # (gpi_conv_loss_fused: the loss gradient stays in LDS); GPI_FUSE_OUT=0 keeps them apart (A/B only)
         self.n_dec_sep = len(self.dec_descs) - (1 if os.environ.get('GPI_FUSE_OUT', '1') != '0' else 0)
         # ---- dense head buffers
-        d_lat = self.dp.input.per_sample
+        self.d_lat = self.dp.input.per_sample
         d_x = g.dim_effective_property if self.N_q > 0 else 1
         self.d_x = d_x
         self.d_y = g.dim_out
         # nonlinear effective-property map (L hidden layers): gpi_gpmlp_forward / _backward own the gp term of the
         # q rows, the head runs without GPI_HEAD_GP.  L = 0: nothing of this exists -- no launch, no buffer.
-        gp_lin = gp_linears(gp) if self.N_x > 0 else []
+        self.gp_lin = gp_lin = gp_linears(gp) if self.N_x > 0 else []
         self.gp_hidden = max(len(gp_lin) - 1, 0)
         check_gp_hidden(self.gp_hidden)
         self.gp_widths = ([gp_lin[0].in_features] + [fc.out_features for fc in gp_lin]) if self.gp_hidden else []
@@ -316,65 +504,59 @@ class ElboEngine(object):
         for key, n in (('sup', self.N_s), ('vo', 0 if self.vo_holdoff else self.N_vo)):
             if n > 0:
                 self.gls_off[key] = ws.parts.alloc(n * self.d_y)
-        ws.materialize(dev)
-        P = lambda mod, n: flat.offset(mod.get_parameter(n))
-        h = L.HeadDesc()
-        h.flags = L.HEAD_LATENT
-        if self.B_u > 0:
-            h.flags |= (L.HEAD_ENC if self.armortized else 0) | L.HEAD_REPARAM
-        gpf = (L.HEAD_GP | (L.HEAD_LOCKX if self.lockx else 0)) if not self.gp_hidden else 0
-        if self.N_s > 0:
-            h.flags |= L.HEAD_QZ | gpf
-        h.n_enc, h.n_q, h.n_q2 = self.B_u, self.N_s, self.N_vo
-        if self.N_vo > 0:
-            h.flags2 = L.HEAD_QZ | (0 if self.vo_holdoff else gpf)
-        h.d_feat, h.d_z, h.d_lat, h.d_x = d_feat, dz, d_lat, d_x
-        if self.B_u > 0 and self.armortized:
-            h.fc_w, h.fc_b = P(enc, 'features.FC.weight'), P(enc, 'features.FC.bias')
-            h.mu_w, h.mu_b = P(enc, 'features.SplitDense.fc_mean.weight'), P(enc, 'features.SplitDense.fc_mean.bias')
-            h.ls_w, h.ls_b = P(enc, 'features.SplitDense.fc_logvar.weight'), P(enc, 'features.SplitDense.fc_logvar.bias')
-            h.feat, h.gfeat = self.ep.output.off, self.ep.output.s_off
-        else:
-            h.fc_w = h.fc_b = h.mu_w = h.mu_b = h.ls_w = h.ls_b = -1
-            h.feat = h.gfeat = 0
-        h.lat_w, h.lat_b = P(dec, 'latent_map.weight'), P(dec, 'latent_map.bias')
-        h.gp_w = h.gp_b = h.gp_ls = h.qz_mu = h.qz_ls = h.qx_mu = h.qx_ls = -1
-        h.qz_mu2 = h.qz_ls2 = h.qx_mu2 = h.qx_ls2 = -1
-        if self.N_x > 0 and not self.gp_hidden:
-            h.gp_w, h.gp_b = P(gp, 'fc.weight'), P(gp, 'fc.bias')
-            if not self.lockx:
-                h.gp_ls = P(gp, 'logsigmas_X')
-        if self.N_s > 0:
-            qz = model.q_z['supervised']
-            h.qz_mu, h.qz_ls = flat.offset(qz._mean), flat.offset(qz._logsigma)
-            if not self.lockx:
-                qx = model.q_X['supervised']
-                h.qx_mu, h.qx_ls = flat.offset(qx._mean), flat.offset(qx._logsigma)
-        if self.N_vo > 0:
-            qz = model.q_z['vo']
-            h.qz_mu2, h.qz_ls2 = flat.offset(qz._mean), flat.offset(qz._logsigma)
-            if not self.vo_holdoff and not self.lockx:
-                qx = model.q_X['vo']
-                h.qx_mu2, h.qx_ls2 = flat.offset(qx._mean), flat.offset(qx._logsigma)
-        for k, v in hb.items():
-            setattr(h, k, v)
-        h.lat, h.glat = self.dp.input.off, self.dp.input.s_off
+        ws.materialize(flat.P.device)
         su = 1.0 / self.B_u if (self.normalize and self.B_u) else 1.0
         ss = 1.0 / self.N_s if (self.normalize and self.N_s) else 1.0
         sv = 1.0 / self.N_vo if (self.normalize and self.N_vo) else 1.0
         self.su, self.ss, self.sv = su, ss, sv
-        h.kl_scale_enc, h.kl_scale_q, h.lx_scale = su, ss, ss
+        # ---- contexts
+        if self.ep is not None:
+            self.ectx = make_ctx(ws, flat, [self.B_u])
+            self.ectx.ext_stride = self.ep.input.per_sample
+        self.dctx = make_ctx(ws, flat, self.dec_sizes)
+        for gi, scale in enumerate([su] * (self.B_u > 0) + [ss] * (self.N_s > 0) + [sv] * (self.N_vo > 0)):
+            self.dctx.loss_scale[gi] = scale
+
+    def _build_head(self):
+        """The dense head's descriptor (head) and the MLP effective-property map's (gpm, or None)."""
+        model, flat, ws, hb, gp, dz = self.model, self.flat, self.ws, self.hb, self.gp, self.dz
+        su, ss, sv = self.su, self.ss, self.sv
+        gp_lin = self.gp_lin
+        gpf = (L.HEAD_GP | (L.HEAD_LOCKX if self.lockx else 0)) if not self.gp_hidden else 0
+        flags = L.HEAD_LATENT
+        if self.B_u > 0:
+            flags |= (L.HEAD_ENC if self.armortized else 0) | L.HEAD_REPARAM
+        if self.N_s > 0:
+            flags |= L.HEAD_QZ | gpf
+        f = dict(flags=flags, n_enc=self.B_u, n_q=self.N_s, n_q2=self.N_vo, d_feat=self.d_feat, d_z=dz,
+                 d_lat=self.d_lat, d_x=self.d_x, lat=self.dp.input.off, glat=self.dp.input.s_off,
+                 kl_scale_enc=su, kl_scale_q=ss, lx_scale=ss, kl_scale_q2=sv, lx_scale2=sv)
+        f.update({k: self._poff(self.dec, n) for k, n in DEC_HEAD.items()})
+        if self.N_vo > 0:
+            f['flags2'] = L.HEAD_QZ | (0 if self.vo_holdoff else gpf)
+        if self.ep is not None:
+            f.update({k: self._poff(self.enc, n) for k, n in ENC_HEAD.items()})
+            f.update(feat=self.ep.output.off, gfeat=self.ep.output.s_off)
+        if self.N_x > 0 and not self.gp_hidden:
+            f.update(gp_w=self._poff(gp, 'fc.weight'), gp_b=self._poff(gp, 'fc.bias'))
+            if not self.lockx:
+                f['gp_ls'] = self._poff(gp, 'logsigmas_X')
+        # q rows: (segment suffix, key, has free-X rows)
+        for sfx, key, n, qx in (('', 'supervised', self.N_s, not self.lockx),
+                                ('2', 'vo', self.N_vo, not self.vo_holdoff and not self.lockx)):
+            if n > 0:
+                q = model.q_z[key]
+                f['qz_mu' + sfx], f['qz_ls' + sfx] = flat.offset(q._mean), flat.offset(q._logsigma)
+                if qx:
+                    q = model.q_X[key]
+                    f['qx_mu' + sfx], f['qx_ls' + sfx] = flat.offset(q._mean), flat.offset(q._logsigma)
         if not self.armortized and self.B_u > 0:
             if self.N_s == 0:
                 raise KeyError("elbo_unsupervised takes the KL of q_z['supervised'] (generative.py:525)")
             # the unsupervised term's KL is q_z['supervised']'s: no KL gradient on q_z['unsupervised'],
             # a second one (scale su) on the supervised rows
-            h.kl_scale_enc = 0.0
-            h.kl_scale_q = ss + su
-        h.kl_scale_q2, h.lx_scale2 = sv, sv
-        h.terms = ws.term_ptr(T_KL_ENC).value
-        h.terms2 = ws.term_ptr(T_KL_Q2).value
-        self.head = h
+            f.update(kl_scale_enc=0.0, kl_scale_q=ss + su)
+        self.head = h = head_desc(hb, ws, second=True, **f)
         self.gpm = None
         if self.gp_hidden:
             m = L.GpMlpDesc()
@@ -385,7 +567,7 @@ class ElboEngine(object):
             for k in range(L.GPMLP_MAX_HIDDEN + 1):
                 m.w[k] = flat.offset(gp_lin[k].weight) if k < len(gp_lin) else -1
                 m.b[k] = flat.offset(gp_lin[k].bias) if k < len(gp_lin) else -1
-            m.gp_ls = P(gp, 'logsigmas_X') if not self.lockx else -1
+            m.gp_ls = self._poff(gp, 'logsigmas_X') if not self.lockx else -1
             for k in ('qx_mu', 'qx_ls', 'qx_mu2', 'qx_ls2', 'qz_mu', 'qz_ls', 'qz_mu2', 'qz_ls2'):
                 setattr(m, k, getattr(h, k))
             m.z, m.eps_z = hb['z'] + self.B_u * dz, hb['eps_z'] + self.B_u * dz
@@ -399,48 +581,37 @@ class ElboEngine(object):
             m.terms = ws.term_ptr(T_LOGL_X).value
             m.terms2 = ws.term_ptr(T_LOGL_X2).value
             self.gpm = m
-        # ---- contexts
+
+    def _build_gemm_items(self):
+        """gemm_items: the dense layers' weight-gradient outer products (none without shared_grads)."""
+        h, hb, dz, d_x = self.head, self.hb, self.dz, self.d_x
+        z_q = hb['z'] + self.B_u * dz           # the q samples' rows of z
+        gi = decoder_latent_gemms(h, hb, self.B)
+        if self.N_x > 0 and not self.gp_hidden:
+            gi.append(gemm_item(hb['gmux'], z_q, self.N_x, d_x, dz, d_x, dz, h.gp_w, h.gp_b))
+        for k in range(1, self.gp_hidden + 2) if self.gp_hidden else ():
+            # layer k of the MLP: sum over rows of delta_k (x) h_{k-1} (delta_{L+1} = gmux, h_0 = z)
+            wo, wi = self.gp_widths[k], self.gp_widths[k - 1]
+            a = hb['gmux'] if k == self.gp_hidden + 1 else self.gp_mlp_buffers['dh%d' % k]
+            b = z_q if k == 1 else self.gp_mlp_buffers['h%d' % (k - 1)]
+            gi.append(gemm_item(a, b, self.N_x, wo, wi, wo, wi, self.gpm.w[k - 1], self.gpm.b[k - 1]))
         if self.ep is not None:
-            self.ectx = make_ctx(ws, flat, [self.B_u])
-            self.ectx.ext_stride = self.ep.input.per_sample
-        self.dctx = make_ctx(ws, flat, self.dec_sizes)
-        for gi, scale in enumerate([su] * (self.B_u > 0) + [ss] * (self.N_s > 0) + [sv] * (self.N_vo > 0)):
-            self.dctx.loss_scale[gi] = scale
-        # ---- gradient reductions
+            gi += encoder_head_gemms(h, hb, self.B_u)
+        self.gemm_items = gemm_array(gi if self.shared_grads else [])
+
+    def _build_roms(self, y_weight):
+        """The ROM descriptors (one launch per labeled / VO term; both on the side stream) and the slab
+        reductions: rom_draw, y_weight, roms / rom / rom_vo, reduce_enc, n_reduce_in, reduce_dec, reduce_items."""
+        model, flat, ws, hb, g, d_x = self.model, self.flat, self.ws, self.hb, self.g, self.d_x
+        ss, sv = self.ss, self.sv
+        offE = lambda n: self._poff(self.enc, n)
         self.reduce_enc = self.ep.reduce_items(offE) if self.ep is not None else []
         # slab-reduction items of the encoder's input conv (the first op; no input BN: one item)
         # (counted per op: 1 for the weight, +1 or +2 for an input BN whose gamma / beta are (not)
         # adjacent; a miscount would leave one of its items to the side stream while the main
         # stream's input-conv backward still writes that slab)
         self.n_reduce_in = self.ep.reduce_counts(offE)[0] if self.ep is not None else 0
-        self.reduce_dec = self.dp.reduce_items(offD)
-        self.reduce_items = self.reduce_enc + self.reduce_dec
-        gi = []
-        B = self.B
 
-        def gemm(a, b, S, M, N, lda, ldb, c, bias, flags=0):
-            it = L.GemmItem()
-            it.a_off, it.b_off, it.c_off, it.bias_off = a, b, c, bias
-            it.S, it.M, it.N, it.lda, it.ldb, it.flags = S, M, N, lda, ldb, flags
-            gi.append(it)
-
-        gemm(self.dp.input.s_off, hb['z'], B, d_lat, dz, d_lat, dz, h.lat_w, h.lat_b)
-        if self.N_x > 0 and not self.gp_hidden:
-            gemm(hb['gmux'], hb['z'] + self.B_u * dz, self.N_x, d_x, dz, d_x, dz, h.gp_w, h.gp_b)
-        for k in range(1, self.gp_hidden + 2) if self.gp_hidden else ():
-            # layer k of the MLP: sum over rows of delta_k (x) h_{k-1} (delta_{L+1} = gmux, h_0 = z)
-            wo, wi = self.gp_widths[k], self.gp_widths[k - 1]
-            a = hb['gmux'] if k == self.gp_hidden + 1 else self.gp_mlp_buffers['dh%d' % k]
-            b = hb['z'] + self.B_u * dz if k == 1 else self.gp_mlp_buffers['h%d' % (k - 1)]
-            gemm(a, b, self.N_x, wo, wi, wo, wi, self.gpm.w[k - 1], self.gpm.b[k - 1])
-        if self.B_u > 0 and self.armortized:
-            gemm(hb['dzmu'], hb['hpre'], self.B_u, dz, d_feat, dz, d_feat, h.mu_w, h.mu_b, 1)
-            gemm(hb['dzls'], hb['hpre'], self.B_u, dz, d_feat, dz, d_feat, h.ls_w, h.ls_b, 1)
-            gemm(hb['dhpre'], h.feat, self.B_u, d_feat, d_feat, d_feat, d_feat, h.fc_w, h.fc_b)
-        if not self.shared_grads:
-            gi = []
-        self.gemm_items = (L.GemmItem * len(gi))(*gi)
-        # ---- ROM (one launch per labeled / VO term; both on the side stream)
         def rom_desc(row0, n, scale, slot):
             r = L.RomDesc()
             rom = g.rom
@@ -505,17 +676,19 @@ class ElboEngine(object):
             self.rom_vo.Y = ws.fptr(hb['y_vo']).value
             self.roms.append(self.rom_vo)
         # the ROMs' d/dlogsigma_y rows are reduced with the decoder slabs (after the ROMs on the side stream)
-        self.reduce_dec = (self.reduce_dec if self.shared_grads else []) + self.rom_reduce
+        dec_items = self.dp.reduce_items(lambda n: self._poff(self.dec, n)) if self.shared_grads else []
+        self.reduce_dec = dec_items + self.rom_reduce
         self.reduce_items = self.reduce_enc + self.reduce_dec
-        self._fixed = (self.B_u, self.N_s, self.N_vo)
+
+    def _build_switches(self, run_mods):
+        """BN running statistics, the scheduling switches (enc_reduce, rom_first, rom_at, side_pre), SyncBN and
+        hand-off state."""
         self._side = None
-        self._pending_join = False
         # BN running statistics: encoder once, decoder once per term in the reference's call order
         # (unsupervised, supervised, vo: generative.py:247-287)
-        run_mods = running_modules or {}
-        self.running = BnRunning([(self.ep, run_mods.get('enc', enc), [(0, self.B_u)]),
-                                  (self.dp, run_mods.get('dec', dec), list(enumerate(self.dec_sizes)))], ws, dev)
-        self._running_pending = False
+        self.running = BnRunning([(self.ep, run_mods.get('enc', self.enc), [(0, self.B_u)]),
+                                  (self.dp, run_mods.get('dec', self.dec), list(enumerate(self.dec_sizes)))],
+                                 self.ws, self.flat.P.device)
         # encoder slab reduction: all on the main stream after the input conv's backward ('main'), or
         # split ('split': the input conv's slabs on the main stream, the rest on the side stream
         # concurrently with the input conv's backward)
@@ -528,9 +701,10 @@ class ElboEngine(object):
         # 0.6277 / 0.6274 / 0.6316 / 0.6342 / 0.6485 vs 'forward' 0.6240 / 0.6255 / 0.6303 / 0.6255 / 0.6336 on
         # two others, r03: kept 'forward')
         self.rom_at = os.environ.get('GPI_ROM_AT', 'forward')
-        self._rom_deferred = False
         self.rom_early_launched = False
-        self._pending_sig = None       # hand-off flag the next main-stream codec call signals
+        # the schedule of the step in flight (forward() -> backward()); its ROM still to run with the backward
+        self._sched = None
+        self._rom_deferred = False
         # callable(side stream handle) launched on the side stream ahead of the ROM (fused step)
         self.side_pre = None
         # SyncBN (set_sync_bn): None = replica-BN, per-rank batch statistics
@@ -574,16 +748,14 @@ class ElboEngine(object):
     def rejoin(self):
         """Main stream waits for the side stream's end (flag hand-off mode; a no-op otherwise)."""
         if self._rejoin_pending:
-            torch.cuda.current_stream().wait_event(self._ev_join2)
+            torch.cuda.current_stream().wait_event(self._ev[E_SIDE])
             self._rejoin_pending = False
 
-    def _head_forward(self, st):
-        _run(_lib().gpi_head_forward, C.byref(self.head), C.c_void_p(self.flat.P.data_ptr()),
-             C.c_void_p(self.ws.t_ws.data_ptr()), st, what='head forward')
-
-    def _head_backward(self, hd, st):
-        _run(_lib().gpi_head_backward, C.byref(hd), C.c_void_p(self.flat.P.data_ptr()),
-             C.c_void_p(self.ws.t_ws.data_ptr()), C.c_void_p(self.flat.gacc.data_ptr()), st, what='head backward')
+    def _head_part(self, part, st):
+        """Head backward of one half of the samples (HEAD_PART_ENC / HEAD_PART_Q: the split rule)."""
+        hd = L.HeadDesc.from_buffer_copy(self.head)
+        hd.flags |= part
+        head_backward(hd, self.flat, self.ws, st)
 
     def _gp_forward(self, st):
         _run(_lib().gpi_gpmlp_forward, C.byref(self.gpm), C.c_void_p(self.flat.P.data_ptr()),
@@ -682,84 +854,80 @@ class ElboEngine(object):
         and term scratch (gpi_step_epilogue).  running: BN running-statistics update 'now' (end of
         the forward), 'defer' (on the side stream during backward) or None."""
         st = stream if stream is not None else L.stream_handle()
-        if self.handoff is not None:
-            # the side stream's one fork of the step, before any of its kernels: its flag waits then
-            # follow this step's signals only (never the previous step's); side_done: by the step counter
-            self._side_stream()
-            if self.side_done is not None:
-                _, e, err = self.handoff
-                _run(_lib().gpi_stream_wait_ge, C.c_void_p(e.data_ptr()), C.c_void_p(self.side_done.data_ptr()),
-                     C.c_void_p(err.data_ptr()) if err is not None else None, C.c_void_p(self._side.cuda_stream),
-                     what='side step gate')
-            else:
-                self._ev_start.record(torch.cuda.current_stream())
-                self._side.wait_event(self._ev_start)
         # early ROM: after the side gate (the previous step's update and epilogue -- q_X, eps_x, the
         # cleared term scratch -- are complete); needs the gate and a scratch this forward does not clear
-        early = (self.rom_draw and bool(self.roms) and self.side_done is not None and not zero_scratch
-                 and not (self.rom_at == 'backward' and not compute_value))
-        self.rom_early_launched = early
-        if early:
-            self.rom_side(C.c_void_p(self._side.cuda_stream))
-            self._ev_join.record(self._side)
-            self._pending_join = True
-        self.forward_a(st, zero_gacc, zero_scratch)
-        # rom_at 'backward': the ROM follows the backward's fork on the side stream (ahead of the
-        # variational samples' head backward that needs it) -- one cross-stream dependency less per
-        # step; only when the value is not read right after the forward
-        self._rom_deferred = bool(self.roms) and self.rom_at == 'backward' and not compute_value
-        if self.roms and not self._rom_deferred and not early:
-            # the ROM solve only feeds the head backward: run it on a side stream,
-            # concurrently with the decoder (fork here, join in backward / value).  The decoder
-            # is enqueued first so that, in a captured graph, the main chain is the fork's first
-            # branch and keeps its hardware queue (each cross-queue dependency costs ~10 us).
-            main = torch.cuda.current_stream()
-            self._side_stream()
-            if self.handoff is not None:
-                self._pending_sig = 0          # folded into forward_b's first decoder conv
-            else:
-                self._ev_fork.record(main)
-            if self.rom_first:
-                self._launch_roms()
-        self.forward_b(st)
-        if self.roms and not self.rom_first and not self._rom_deferred and not early:
-            self._launch_roms()
-        if running == 'now':
-            self.running.launch(st)
-        self._running_pending = running == 'defer'
-        if compute_value:
-            self._join()
-            return self.elbo_value()
-        return None
+        early = self.rom_draw and self.side_done is not None and not zero_scratch
+        self._sched = self.schedule(compute_value, running, early)
+        self.rom_early_launched = self._sched.forward[0].stream == SIDE
+        self._rom_deferred = any(s.args.get('rom') for s in self._sched.backward)
+        joiner = self._joiner(st)
+        joiner.begin()
+        self._walk(self._sched.forward, joiner, forward_a=dict(zero_gacc=zero_gacc, zero_scratch=zero_scratch))
+        return self.elbo_value() if compute_value else None
 
-    # The step's pieces, per stream, between its cross-stream dependencies (forward / backward
-    # compose them with events; FusedElboStep's segment capture records each as its own
-    # single-stream graph).
+    def backward(self, stream=None, side_extra=None, main_wait=True):
+        """Gradients of -ELBO into flat.gacc (fp64).  side_extra(side_stream_handle) is launched on
+        the side stream after the decoder's reductions, concurrently with the encoder backward (the
+        fused step draws the next step's subset, noise and decoder dropout masks there; nothing it
+        writes may be read by the encoder backward).  main_wait=False (flag hand-off only): the main
+        stream does not wait for the side stream's end here -- the caller's next launch does
+        (gpi_step_epilogue_adam wait_flag)."""
+        st = stream if stream is not None else L.stream_handle()
+        joiner = self._joiner(st, main_wait)
+        self._walk(self._sched.backward, joiner, backward_side_a=dict(side_extra=side_extra))
+        self._rom_deferred = False
+        joiner.end()
+
+    def schedule(self, compute_value, running, early=False, segments=False):
+        """The step's schedule table (gpi.schedule) for the engine's switches as they stand now.  segments: the
+        table FusedElboStep's segment graphs are captured from, which has no rom_at / rom_first arm."""
+        return step_schedule(self.n_enc_conv, bool(self.roms), self.enc_reduce,
+                             'forward' if segments else self.rom_at, not segments and self.rom_first, early,
+                             compute_value, running)
+
+    def _joiner(self, st, main_wait=True):
+        side = self._side_stream()
+        streams = {MAIN: (torch.cuda.current_stream(), st), SIDE: (side, C.c_void_p(side.cuda_stream))}
+        events = EventJoiner(self._ev, streams)
+        return events if self.handoff is None else FlagJoiner(self, events, main_wait)
+
+    def _walk(self, rows, joiner, **extra):
+        """Walk schedule rows with a joiner; extra: run-time keyword arguments per piece."""
+        def run(s, sig):
+            kw = dict(s.args, **extra.get(s.piece, {}))
+            if sig is not None:
+                kw['sig'] = sig
+            getattr(self, s.piece)(joiner.streams[s.stream][1], **kw)
+        walk(rows, joiner, run)
+
+    # The step's pieces, per stream, between its cross-stream dependencies (gpi.schedule says which follows
+    # which; the joiners realise the edges between them).
     def forward_a(self, st, zero_gacc=True, zero_scratch=True):
         """Main stream, up to the ROM fork: scratch / accumulator reset, encoder forward, head forward."""
-        lib = _lib()
         if zero_scratch:
             self.ws.zero_scratch()
         if zero_gacc:
             self.flat.gacc.zero_()
         if self.ep is not None:
-            self._codec_forward(self.enc_descs, 0, self.n_enc_conv, self.ectx, st, 'encoder forward')
+            self._codec(True, self.enc_descs, 0, self.n_enc_conv, self.ectx, st, 'encoder forward')
         if not self.armortized and self.B_u > 0:
             # q_z['unsupervised'] rows as the "encoder" outputs of the head's first segment
             # (torch copies on the current stream, which the launches use)
             self.ws.view(self.hb['zmu'], self.B_u, self.dz).copy_(self.q_unsup._mean.detach())
             self.ws.view(self.hb['zls'], self.B_u, self.dz).copy_(self.q_unsup._logsigma.detach())
-        assert lib is not None
-        self._head_forward(st)
+        head_forward(self.head, self.flat, self.ws, st)
 
-    def forward_b(self, st):
-        """Main stream: decoder forward and its fused output conv (forward + loss + backward)."""
-        lib = _lib()
-        sig, self._pending_sig = self._pending_sig, None
-        self._codec_forward(self.dec_descs, self.dec0, self.n_dec_sep, self.dctx, st, 'decoder forward', sig=sig)
+    def forward_b(self, st, sig=None):
+        """Main stream: decoder forward and its fused output conv (forward + loss + backward); sig: hand-off
+        flag its first launch signals."""
+        self._codec(True, self.dec_descs, 0, self.n_dec_sep, self.dctx, st, 'decoder forward', sig=sig)
         if self.n_dec_sep < len(self.dec_descs):
-            _run(lib.gpi_conv_loss_fused, C.byref(self.dec_descs[self.n_dec_sep]), C.byref(self.dctx), st,
+            _run(_lib().gpi_conv_loss_fused, C.byref(self.dec_descs[self.n_dec_sep]), C.byref(self.dctx), st,
                  what='decoder output conv (forward + loss + backward)')
+
+    def running_now(self, st):
+        """Main stream, end of the forward: the BN running statistics (running='now')."""
+        self.running.launch(st)
 
     def rom_side(self, sst):
         """Side stream: the ROM solves (after the head forward); with the MLP effective-property map its
@@ -774,15 +942,13 @@ class ElboEngine(object):
     def backward_a(self, st, split):
         """Main stream: decoder backward and the head backward (encoder samples only when split:
         the variational samples' need the ROM adjoint and follow it on the side stream)."""
-        self._codec_backward(self.dec_descs, self.dec0, self.n_dec_sep, self.dctx, st, 'decoder backward')
+        self._codec(False, self.dec_descs, 0, self.n_dec_sep, self.dctx, st, 'decoder backward')
         if split:
-            hd = L.HeadDesc.from_buffer_copy(self.head)
-            hd.flags |= L.HEAD_PART_ENC
-            self._head_backward(hd, st)
+            self._head_part(L.HEAD_PART_ENC, st)
         else:
             if self.gpm is not None:
                 self._gp_backward(st)
-            self._head_backward(self.head, st)
+            head_backward(self.head, self.flat, self.ws, st)
         if not self.armortized and self.B_u > 0:
             # d/dmu, d/dlogsigma of q_z['unsupervised'] (written by the head for its first segment)
             n = self.B_u * self.dz
@@ -794,7 +960,7 @@ class ElboEngine(object):
         """Main stream: every encoder conv's backward but the input conv's (reverse order); sig: hand-off
         flag its first launch signals."""
         if self.ep is not None and self.n_enc_conv > 1:
-            self._codec_backward(self.enc_descs, 1, self.n_enc_conv, self.ectx, st, 'encoder backward', sig=sig)
+            self._codec(False, self.enc_descs, 1, self.n_enc_conv, self.ectx, st, 'encoder backward', sig=sig)
         elif sig is not None:
             self._signal(sig, st)
 
@@ -814,27 +980,21 @@ class ElboEngine(object):
                  what='In_conv backward')
         run_reduce(self.reduce_enc[:self.n_reduce_in] if enc_split else self.reduce_enc, self.ws, self.flat, st)
 
-    def backward_side_a(self, sst, split, side_extra=None):
-        """Side stream, after the decoder backward: the variational samples' head backward (split),
-        the decoder slab reduction, the deferred BN running statistics, the dense weight GEMM and
-        side_extra."""
-        lib = _lib()
-        if self._rom_deferred:
+    def backward_side_a(self, sst, split, rom=False, running=False, side_extra=None):
+        """Side stream, after the decoder backward: the deferred ROM (rom), the variational samples' head
+        backward (split), the decoder slab reduction, the deferred BN running statistics (running), the dense
+        weight GEMM and side_extra."""
+        if rom:
             self.rom_side(sst)
-            self._rom_deferred = False
         if split:
             if self.gpm is not None:
                 self._gp_backward(sst)          # needs the ROM adjoint, as the head's variational half
-            hq = L.HeadDesc.from_buffer_copy(self.head)
-            hq.flags |= L.HEAD_PART_Q
-            self._head_backward(hq, sst)
+            self._head_part(L.HEAD_PART_Q, sst)
         run_reduce(self.reduce_dec, self.ws, self.flat, sst)
-        if self._running_pending:
+        if running:
             self.running.launch(sst)
-            self._running_pending = False
         if len(self.gemm_items):
-            _run(lib.gpi_outer_gemm, self.gemm_items, len(self.gemm_items), C.c_void_p(self.ws.t_ws.data_ptr()),
-                 C.c_void_p(self.flat.gacc.data_ptr()), sst, what='outer gemm')
+            outer_gemm(self.gemm_items, self.flat, self.ws, sst)
         if side_extra is not None:
             side_extra(sst)
 
@@ -908,8 +1068,9 @@ class ElboEngine(object):
     def _codec_kind(self, descs):
         return 'enc' if self.ep is not None and descs is self.enc_descs else 'dec'
 
-    def _codec_forward(self, descs, i0, i1, ctx, st, what, sig=None):
-        """descs[i0] .. descs[i1 - 1]; sig: hand-off flag the first launch signals (gpi_codec_forward_sig)."""
+    def _codec(self, fwd, descs, i0, i1, ctx, st, what, sig=None):
+        """The convs descs[i0] .. descs[i1 - 1] forward (fwd), or descs[i1 - 1] down to descs[i0] backward
+        (gpi_codec_backward's order); sig: hand-off flag the first launch signals (the *_sig entry points)."""
         lib = _lib()
         sa = self._sig_args(sig) if sig is not None else (None, None)
         if i1 <= i0:
@@ -918,59 +1079,26 @@ class ElboEngine(object):
             return
         if self.bn_sync is None:
             ptr = C.cast(C.byref(descs, i0 * C.sizeof(L.ConvDesc)), C.POINTER(L.ConvDesc))
-            _run(lib.gpi_codec_forward_sig, ptr, i1 - i0, C.byref(ctx), *sa, st, what=what)
+            _run(lib.gpi_codec_forward_sig if fwd else lib.gpi_codec_backward_sig, ptr, i1 - i0, C.byref(ctx), *sa,
+                 st, what=what)
             return
         kind = self._codec_kind(descs)
-        for i in range(i0, i1):
+        order = range(i0, i1) if fwd else range(i1 - 1, i0 - 1, -1)
+        for i in order:
             d = descs[i]
-            _run(lib.gpi_conv_forward_sig, C.byref(d), C.byref(ctx), *(sa if i == i0 else (None, None)), st,
-                 what=what)
-            if d.epilogue == L.EPI_STORE_STATS and d.out_stat >= 0:
+            if not fwd and d.gout_mode == 0:          # its output feeds a BN: that BN's backward sums are complete
+                self._sync_stats(d.out_stat, d.cout, 2, kind)
+            _run(lib.gpi_conv_forward_sig if fwd else lib.gpi_conv_backward_sig, C.byref(d), C.byref(ctx),
+                 *(sa if i == order[0] else (None, None)), st, what=what)
+            if fwd and d.epilogue == L.EPI_STORE_STATS and d.out_stat >= 0:
                 self._sync_stats(d.out_stat, d.cout, 0, kind)
 
-    def _codec_backward(self, descs, i0, i1, ctx, st, what, sig=None):
-        """descs[i1 - 1] down to descs[i0] (gpi_codec_backward's order); sig: hand-off flag the first
-        launch signals."""
-        lib = _lib()
-        sa = self._sig_args(sig) if sig is not None else (None, None)
-        if i1 <= i0:
-            if sig is not None:
-                self._signal(sig, st)
-            return
-        if self.bn_sync is None:
-            ptr = C.cast(C.byref(descs, i0 * C.sizeof(L.ConvDesc)), C.POINTER(L.ConvDesc))
-            _run(lib.gpi_codec_backward_sig, ptr, i1 - i0, C.byref(ctx), *sa, st, what=what)
-            return
-        kind = self._codec_kind(descs)
-        for i in range(i1 - 1, i0 - 1, -1):
-            d = descs[i]
-            if d.gout_mode == 0:          # its output feeds a BN: that BN's backward sums are complete
-                self._sync_stats(d.out_stat, d.cout, 2, kind)
-            _run(lib.gpi_conv_backward_sig, C.byref(d), C.byref(ctx), *(sa if i == i1 - 1 else (None, None)), st,
-                 what=what)
-
-    def _launch_roms(self):
-        if self.handoff is not None:
-            self._wait(0, C.c_void_p(self._side.cuda_stream))
-        else:
-            self._side.wait_event(self._ev_fork)
-        self.rom_side(C.c_void_p(self._side.cuda_stream))
-        self._ev_join.record(self._side)
-        self._pending_join = True
-
     def _side_stream(self):
+        """The side stream and, with it, the events of the schedule's edges (and of the step gate)."""
         if self._side is None:
             self._side = torch.cuda.Stream(device=torch.cuda.current_stream().device)
-            self._ev_fork, self._ev_join = torch.cuda.Event(), torch.cuda.Event()
-            self._ev_fork2, self._ev_join2 = torch.cuda.Event(), torch.cuda.Event()
-            self._ev_enc = torch.cuda.Event()
-            self._ev_start = torch.cuda.Event()
+            self._ev = {k: torch.cuda.Event() for k in (E_ROM, E_DEC, E_ENC, E_SIDE, E_VALUE, 'start')}
         return self._side
-
-    def _join(self):
-        if self._pending_join:
-            torch.cuda.current_stream().wait_event(self._ev_join)
-            self._pending_join = False
 
     def _check_rom_written(self):
         if self._rom_deferred:
@@ -1035,70 +1163,6 @@ class ElboEngine(object):
                     out['vo_entropy'] = float(t[T_ENT2]) + self.N_vo * ENT_CONST
         return out
 
-    def backward(self, stream=None, side_extra=None, main_wait=True):
-        """Gradients of -ELBO into flat.gacc (fp64).  side_extra(side_stream_handle) is launched on
-        the side stream after the decoder's reductions, concurrently with the encoder backward (the
-        fused step draws the next step's subset, noise and decoder dropout masks there; nothing it
-        writes may be read by the encoder backward).  main_wait=False (flag hand-off only): the main
-        stream does not wait for the side stream's end here -- the caller's next launch does
-        (gpi_step_epilogue_adam wait_flag)."""
-        st = stream if stream is not None else L.stream_handle()
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        # With the ROM still pending on the side stream, only the encoder samples' head backward
-        # runs on the main stream; the variational samples' (which need the ROM adjoint) follow
-        # the ROM on the side stream, so the main chain never waits for the ROM.
-        split = self._pending_join or self._rom_deferred
-        flags = self.handoff is not None
-        sst = C.c_void_p(side.cuda_stream)
-        self.backward_a(st, split)
-        # the decoder's slab reduction and the dense weight gradients depend only on what is
-        # done by now: run them on the side stream, concurrently with the encoder backward
-        # (enqueued after it, so the encoder stays on the main chain's queue in a graph)
-        if not flags:
-            self._ev_fork2.record(main)
-        n_enc = len(self.enc_descs) if self.ep is not None else 0
-        enc_split = n_enc and self.enc_reduce == 'split'
-        if n_enc:
-            # flags: the encoder backward's first conv signals flag 1 (the head backward is done), the
-            # input conv's backward flag 2 (the rest of the encoder backward is done)
-            self.backward_b(st, sig=1 if flags else None)
-            if enc_split and not flags:
-                self._ev_enc.record(main)
-            self.backward_c(st, enc_split, sig=2 if (flags and enc_split) else None)
-        elif flags:
-            self._signal(1, st)
-        # (captured ahead of the encoder backward instead, the side branch took the launch stream
-        # and the main chain the pooled one: 0.7526 vs 0.6289 ms per step, r03)
-        if flags:
-            self._wait(1, sst)
-        else:
-            side.wait_event(self._ev_fork2)
-        self.backward_side_a(sst, split, side_extra)
-        if split:
-            self._pending_join = False          # joined below with the rest of the side work
-        if enc_split:
-            if flags:
-                self._wait(2, sst)
-            else:
-                side.wait_event(self._ev_enc)
-            self.backward_side_b(sst)
-        if flags:
-            # the side's end by flag on the main chain (a wait launch, or folded into the caller's
-            # epilogue: main_wait False); the event join (capture legality) after the step's last
-            # kernel: rejoin()
-            self._signal(3, sst)
-            if main_wait:
-                self._wait(3, st)
-            if self.side_done is not None:
-                _run(_lib().gpi_rng_advance, C.c_void_p(self.side_done.data_ptr()), 1, sst, what='side step done')
-            else:
-                self._ev_join2.record(side)
-                self._rejoin_pending = True
-        else:
-            self._ev_join2.record(side)
-            main.wait_event(self._ev_join2)
-
     def finalize(self, out, accumulate=False, step=None, stream=None, zero_acc=False):
         st = stream if stream is not None else L.stream_handle()
         flags = (L.FINALIZE_ACCUMULATE if accumulate else 0) | (L.FINALIZE_ZERO if zero_acc else 0)
@@ -1119,46 +1183,10 @@ class EncoderEngine(object):
     """CNNEncoder.forward (Encoder.py:191-196): x -> (mean, logsigma) and its backward."""
 
     def __init__(self, enc, flat, B):
-        self.flat, self.B = flat, int(B)
-        ws = Workspace()
-        self.ws = ws
-        off = lambda n: flat.offset(enc.get_parameter(n))
-        self.p = encoder_program(**enc.native_config())
-        self.descs = self.p.layout(self.B, ws.ws, ws.stats, ws.parts, groups_struct([self.B]), off)
-        d_feat, dz = self.p.d_feat, enc.latent_dim
-        self.dz = dz
-        hb = {k: ws.alloc(self.B * n) for k, n in (('hpre', d_feat), ('dhpre', d_feat), ('zmu', dz), ('zls', dz),
-                                                    ('eps_z', dz), ('z', dz), ('gz', dz), ('dzmu', dz),
-                                                    ('dzls', dz))}
-        hb.update({k: 0 for k in ('eps_x', 'xs', 'mux', 'gxs', 'gmux')})
-        ws.materialize(flat.P.device)
-        h = L.HeadDesc()
-        h.flags = L.HEAD_ENC
-        h.n_enc, h.n_q, h.d_feat, h.d_z, h.d_lat, h.d_x = self.B, 0, d_feat, dz, 1, 1
-        h.fc_w, h.fc_b = off('features.FC.weight'), off('features.FC.bias')
-        h.mu_w, h.mu_b = off('features.SplitDense.fc_mean.weight'), off('features.SplitDense.fc_mean.bias')
-        h.ls_w, h.ls_b = off('features.SplitDense.fc_logvar.weight'), off('features.SplitDense.fc_logvar.bias')
-        h.lat_w = h.lat_b = h.gp_w = h.gp_b = h.gp_ls = h.qz_mu = h.qz_ls = h.qx_mu = h.qx_ls = -1
-        for k, v in hb.items():
-            setattr(h, k, v)
-        h.feat, h.gfeat = self.p.output.off, self.p.output.s_off
-        h.lat = h.glat = 0
-        h.kl_scale_enc = h.kl_scale_q = h.lx_scale = 1.0
-        h.terms = ws.term_ptr(T_KL_ENC).value
-        self.head, self.hb = h, hb
-        self.ctx = make_ctx(ws, flat, [self.B])
-        self.ctx.ext_stride = self.p.input.per_sample
-        items = self.p.reduce_items(off)
-        self.reduce_items = items
-        gi = []
-        for a, c, b in ((hb['dzmu'], h.mu_w, h.mu_b), (hb['dzls'], h.ls_w, h.ls_b)):
-            it = L.GemmItem(a_off=a, b_off=hb['hpre'], c_off=c, bias_off=b, S=self.B, M=dz, N=d_feat, lda=dz,
-                            ldb=d_feat, flags=1)
-            gi.append(it)
-        gi.append(L.GemmItem(a_off=hb['dhpre'], b_off=h.feat, c_off=h.fc_w, bias_off=h.fc_b, S=self.B, M=d_feat,
-                             N=d_feat, lda=d_feat, ldb=d_feat, flags=0))
-        self.gemm_items = (L.GemmItem * len(gi))(*gi)
-        self.running = BnRunning([(self.p, enc, [(0, self.B)])], ws, flat.P.device)
+        off = codec_setup(self, 'enc', enc, flat, B)
+        self.reduce_items = self.p.reduce_items(off)
+        self.gemm_items = gemm_array(encoder_head_gemms(self.head, self.hb, self.B))
+        self.running = BnRunning([(self.p, enc, [(0, self.B)])], self.ws, flat.P.device)
 
     def forward(self, x, dropout=None, seed=0):
         """dropout: optional injected channel scales {conv name: [B, cout]} (else drawn, seed)."""
@@ -1176,61 +1204,31 @@ class EncoderEngine(object):
         self.ws.zero_scratch()
         _run(lib.gpi_codec_forward, self.descs, len(self.descs), C.byref(self.ctx), st, what='encoder forward')
         self.running.launch(st)
-        _run(lib.gpi_head_forward, C.byref(self.head), C.c_void_p(self.flat.P.data_ptr()),
-             C.c_void_p(self.ws.t_ws.data_ptr()), st, what='head forward')
+        head_forward(self.head, self.flat, self.ws, st)
         return (self.ws.view(self.hb['zmu'], self.B, self.dz).clone(),
                 self.ws.view(self.hb['zls'], self.B, self.dz).clone())
 
     def backward(self, dmu, dls):
-        lib, st = _lib(), L.stream_handle()
+        st = L.stream_handle()
         self.ws.view(self.hb['gz'], self.B, self.dz).copy_(dmu)
         self.ws.view(self.hb['dzls'], self.B, self.dz).copy_(dls)
         self.flat.gacc.zero_()
-        _run(lib.gpi_head_backward, C.byref(self.head), C.c_void_p(self.flat.P.data_ptr()),
-             C.c_void_p(self.ws.t_ws.data_ptr()), C.c_void_p(self.flat.gacc.data_ptr()), st, what='head backward')
-        _run(lib.gpi_codec_backward, self.descs, len(self.descs), C.byref(self.ctx), st, what='encoder backward')
+        head_backward(self.head, self.flat, self.ws, st)
+        _run(_lib().gpi_codec_backward, self.descs, len(self.descs), C.byref(self.ctx), st, what='encoder backward')
         run_reduce(self.reduce_items, self.ws, self.flat, st)
-        _run(lib.gpi_outer_gemm, self.gemm_items, len(self.gemm_items), C.c_void_p(self.ws.t_ws.data_ptr()),
-             C.c_void_p(self.flat.gacc.data_ptr()), st, what='outer gemm')
+        outer_gemm(self.gemm_items, self.flat, self.ws, st)
 
 
 class DecoderEngine(object):
     """CNNDecoder.forward (Decoder.py:288-305): z -> (mean, logsigma) [B, H, W] and its backward."""
 
     def __init__(self, dec, flat, B):
-        self.flat, self.B = flat, int(B)
-        ws = Workspace()
-        self.ws = ws
-        off = lambda n: flat.offset(dec.get_parameter(n))
-        self.p = decoder_program(final_epilogue=None, **dec.native_config())
-        self.descs = self.p.layout(self.B, ws.ws, ws.stats, ws.parts, groups_struct([self.B]), off)
-        dz = dec.dim_latent
-        self.dz = dz
-        d_lat = self.p.input.per_sample
-        hb = {k: ws.alloc(self.B * dz) for k in ('zmu', 'zls', 'eps_z', 'z', 'gz', 'dzmu', 'dzls')}
-        hb.update({k: 0 for k in ('hpre', 'dhpre', 'eps_x', 'xs', 'mux', 'gxs', 'gmux')})
-        ws.materialize(flat.P.device)
-        h = L.HeadDesc()
-        h.flags = L.HEAD_LATENT
-        h.n_enc, h.n_q, h.d_feat, h.d_z, h.d_lat, h.d_x = self.B, 0, 1, dz, d_lat, 1
-        h.fc_w = h.fc_b = h.mu_w = h.mu_b = h.ls_w = h.ls_b = -1
-        h.gp_w = h.gp_b = h.gp_ls = h.qz_mu = h.qz_ls = h.qx_mu = h.qx_ls = -1
-        h.lat_w, h.lat_b = off('latent_map.weight'), off('latent_map.bias')
-        for k, v in hb.items():
-            setattr(h, k, v)
-        h.feat = h.gfeat = 0
-        h.lat, h.glat = self.p.input.off, self.p.input.s_off
-        h.kl_scale_enc = h.kl_scale_q = h.lx_scale = 1.0
-        h.terms = ws.term_ptr(T_KL_ENC).value
-        self.head, self.hb = h, hb
-        self.ctx = make_ctx(ws, flat, [self.B])
-        items = self.p.reduce_items(off)
-        self.reduce_items = items
-        self.gemm_items = (L.GemmItem * 1)(L.GemmItem(a_off=h.glat, b_off=hb['z'], c_off=h.lat_w, bias_off=h.lat_b,
-                                                      S=self.B, M=d_lat, N=dz, lda=d_lat, ldb=dz, flags=0))
+        off = codec_setup(self, 'dec', dec, flat, B)
+        self.reduce_items = self.p.reduce_items(off)
+        self.gemm_items = gemm_array(decoder_latent_gemms(self.head, self.hb, self.B))
         o = self.p.output
         self.out_shape = (self.B, o.C, o.H, o.W)
-        self.running = BnRunning([(self.p, dec, [(0, self.B)])], ws, flat.P.device)
+        self.running = BnRunning([(self.p, dec, [(0, self.B)])], self.ws, flat.P.device)
 
     def forward(self, z, dropout=None, seed=0):
         """dropout: optional injected channel scales {conv name: [B, cout]} (else drawn, seed)."""
@@ -1243,22 +1241,19 @@ class DecoderEngine(object):
             else:
                 draw_dropout(self.ws, (self.p,), st, seed)
         self.ws.zero_scratch()
-        _run(lib.gpi_head_forward, C.byref(self.head), C.c_void_p(self.flat.P.data_ptr()),
-             C.c_void_p(self.ws.t_ws.data_ptr()), st, what='latent map')
+        head_forward(self.head, self.flat, self.ws, st, what='latent map')
         _run(lib.gpi_codec_forward, self.descs, len(self.descs), C.byref(self.ctx), st, what='decoder forward')
         self.running.launch(st)
         return self.ws.view(self.p.output.off, *self.out_shape).clone()
 
     def backward(self, dout):
-        lib, st = _lib(), L.stream_handle()
+        st = L.stream_handle()
         self.ws.view(self.p.output.s_off, *self.out_shape).copy_(dout)
         self.flat.gacc.zero_()
-        _run(lib.gpi_codec_backward, self.descs, len(self.descs), C.byref(self.ctx), st, what='decoder backward')
-        _run(lib.gpi_head_backward, C.byref(self.head), C.c_void_p(self.flat.P.data_ptr()),
-             C.c_void_p(self.ws.t_ws.data_ptr()), C.c_void_p(self.flat.gacc.data_ptr()), st, what='latent map bwd')
+        _run(_lib().gpi_codec_backward, self.descs, len(self.descs), C.byref(self.ctx), st, what='decoder backward')
+        head_backward(self.head, self.flat, self.ws, st, what='latent map bwd')
         run_reduce(self.reduce_items, self.ws, self.flat, st)
-        _run(lib.gpi_outer_gemm, self.gemm_items, len(self.gemm_items), C.c_void_p(self.ws.t_ws.data_ptr()),
-             C.c_void_p(self.flat.gacc.data_ptr()), st, what='outer gemm')
+        outer_gemm(self.gemm_items, self.flat, self.ws, st)
         return self.ws.view(self.hb['dzmu'], self.B, self.dz).clone()
 
 

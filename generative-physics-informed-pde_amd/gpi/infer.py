@@ -21,9 +21,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import (Workspace, groups_struct, make_ctx, rom_call, _run, _lib, T_KL_ENC, ROM_NN, gp_linears,
-                     check_gp_hidden)
-from .plan import encoder_program, decoder_program
+from .engine import codec_setup, head_forward, rom_call, _run, _lib, ROM_NN, gp_linears, check_gp_hidden
 
 
 class BnEvalSeed(object):
@@ -78,50 +76,13 @@ class BnEvalSeed(object):
                  self.ws.n_stats, stream, what='bn eval seed')
 
 
-def _head_desc(hb, off_names, off):
-    h = L.HeadDesc()
-    for k in ('fc_w', 'fc_b', 'mu_w', 'mu_b', 'ls_w', 'ls_b', 'lat_w', 'lat_b', 'gp_w', 'gp_b', 'gp_ls', 'qz_mu',
-              'qz_ls', 'qx_mu', 'qx_ls'):
-        setattr(h, k, -1)
-    for k, name in off_names.items():
-        setattr(h, k, off(name))
-    for k, v in hb.items():
-        setattr(h, k, v)
-    h.kl_scale_enc = h.kl_scale_q = h.lx_scale = 1.0
-    return h
-
-
 class EvalEncoderEngine(object):
     """CNNEncoder.forward in eval mode: x -> (mean, logsigma), forward only."""
     mode = 'eval'
 
     def __init__(self, enc, flat, B):
-        self.flat, self.B = flat, int(B)
-        dev = flat.P.device
-        ws = Workspace()
-        self.ws = ws
-        off = lambda n: flat.offset(enc.get_parameter(n))
-        self.p = encoder_program(**enc.native_config())
-        self.descs = self.p.layout(self.B, ws.ws, ws.stats, ws.parts, groups_struct([self.B]), off, eval_mode=True)
-        d_feat, dz = self.p.d_feat, enc.latent_dim
-        self.dz = dz
-        hb = {k: ws.alloc(self.B * n) for k, n in (('hpre', d_feat), ('dhpre', d_feat), ('zmu', dz), ('zls', dz),
-                                                    ('eps_z', dz), ('z', dz), ('gz', dz), ('dzmu', dz),
-                                                    ('dzls', dz))}
-        hb.update({k: 0 for k in ('eps_x', 'xs', 'mux', 'gxs', 'gmux')})
-        ws.materialize(dev)
-        h = _head_desc(hb, dict(fc_w='features.FC.weight', fc_b='features.FC.bias',
-                                mu_w='features.SplitDense.fc_mean.weight', mu_b='features.SplitDense.fc_mean.bias',
-                                ls_w='features.SplitDense.fc_logvar.weight',
-                                ls_b='features.SplitDense.fc_logvar.bias'), off)
-        h.flags = L.HEAD_ENC
-        h.n_enc, h.n_q, h.d_feat, h.d_z, h.d_lat, h.d_x = self.B, 0, d_feat, dz, 1, 1
-        h.feat, h.gfeat = self.p.output.off, 0
-        h.lat = h.glat = 0
-        h.terms = ws.term_ptr(T_KL_ENC).value
-        self.head, self.hb = h, hb
-        self.ctx = make_ctx(ws, flat, [self.B])
-        self.ctx.ext_stride = self.p.input.per_sample
+        codec_setup(self, 'enc', enc, flat, B, train=False)
+        ws, hb, dz, dev = self.ws, self.hb, self.dz, flat.P.device
         self.seed = BnEvalSeed(self.p, enc, self.B, ws, dev)
         self.mu = ws.view(hb['zmu'], self.B, dz)
         self.logsigma = ws.view(hb['zls'], self.B, dz)
@@ -132,11 +93,10 @@ class EvalEncoderEngine(object):
         self._x = x
         self.ctx.ext_in = x.data_ptr()
         self.ctx.ext_idx = None
-        lib = _lib()
         self.seed.launch(st)
-        _run(lib.gpi_codec_forward, self.descs, len(self.descs), C.byref(self.ctx), st, what='encoder eval forward')
-        _run(lib.gpi_head_forward, C.byref(self.head), C.c_void_p(self.flat.P.data_ptr()),
-             C.c_void_p(self.ws.t_ws.data_ptr()), st, what='head forward')
+        _run(_lib().gpi_codec_forward, self.descs, len(self.descs), C.byref(self.ctx), st,
+             what='encoder eval forward')
+        head_forward(self.head, self.flat, self.ws, st)
 
     def forward(self, x):
         L.require_device(x)
@@ -155,41 +115,20 @@ class EvalDecoderEngine(object):
     mode = 'eval'
 
     def __init__(self, dec, flat, B):
-        self.flat, self.B = flat, int(B)
+        codec_setup(self, 'dec', dec, flat, B, train=False)
         self.binary = bool(getattr(dec, '_binary', False))
-        dev = flat.P.device
-        ws = Workspace()
-        self.ws = ws
-        off = lambda n: flat.offset(dec.get_parameter(n))
-        self.p = decoder_program(final_epilogue=None, **dec.native_config())
-        self.descs = self.p.layout(self.B, ws.ws, ws.stats, ws.parts, groups_struct([self.B]), off, eval_mode=True)
-        dz = dec.dim_latent
-        self.dz = dz
-        d_lat = self.p.input.per_sample
-        hb = {k: ws.alloc(self.B * dz) for k in ('zmu', 'zls', 'eps_z', 'z', 'gz', 'dzmu', 'dzls')}
-        hb.update({k: 0 for k in ('hpre', 'dhpre', 'eps_x', 'xs', 'mux', 'gxs', 'gmux')})
-        ws.materialize(dev)
-        h = _head_desc(hb, dict(lat_w='latent_map.weight', lat_b='latent_map.bias'), off)
-        h.flags = L.HEAD_LATENT
-        h.n_enc, h.n_q, h.d_feat, h.d_z, h.d_lat, h.d_x = self.B, 0, 1, dz, d_lat, 1
-        h.feat = h.gfeat = 0
-        h.lat, h.glat = self.p.input.off, 0
-        h.terms = ws.term_ptr(T_KL_ENC).value
-        self.head, self.hb = h, hb
-        self.ctx = make_ctx(ws, flat, [self.B])
         o = self.p.output
         self.out_shape = (self.B, o.C, o.H, o.W)
-        self.seed = BnEvalSeed(self.p, dec, self.B, ws, dev)
+        self.seed = BnEvalSeed(self.p, dec, self.B, self.ws, flat.P.device)
 
     def forward(self, z):
         L.require_device(z)
-        lib, st = _lib(), L.stream_handle()
+        st = L.stream_handle()
         self.seed.refresh()
         self.ws.view(self.hb['z'], self.B, self.dz).copy_(z)
-        _run(lib.gpi_head_forward, C.byref(self.head), C.c_void_p(self.flat.P.data_ptr()),
-             C.c_void_p(self.ws.t_ws.data_ptr()), st, what='latent map')
+        head_forward(self.head, self.flat, self.ws, st, what='latent map')
         self.seed.launch(st)
-        _run(lib.gpi_codec_forward, self.descs, len(self.descs), C.byref(self.ctx), st, what='decoder eval forward')
+        _run(_lib().gpi_codec_forward, self.descs, len(self.descs), C.byref(self.ctx), st, what='decoder eval forward')
         out = self.ws.view(self.p.output.off, *self.out_shape)
         return torch.sigmoid(out) if self.binary else out.clone()
 

@@ -18,6 +18,7 @@ import torch.distributed as dist
 from . import _lib as L
 from . import vo as gvo
 from .engine import ElboEngine
+from .schedule import MAIN, SIDE, E_ROM, E_DEC, E_ENC, E_SIDE, segments
 
 # Philox sub ids of the virtual-observable targets y ~ N(VO.mean, VO.var) (generative.py:356).  The step's
 # draws use sub0 + {1 subset, 2 eps_z, 3 eps_X, 4 / 5 encoder / decoder Dropout2d, 6 y_vo} with sub0 = 0
@@ -609,8 +610,8 @@ class FusedElboStep(object):
         return g_fb, g_side
 
     def _capture_segments(self):
-        """The step as single-stream graphs, one per stretch of a stream between two cross-stream
-        dependencies, replayed with events between them (_replay_segments).  A HIP graph whose
+        """The segment joiner: the step as single-stream graphs, one per stretch of the schedule table
+        (gpi.schedule.segments), replayed with events for the table's edges (_replay_segments).  A HIP graph whose
         nodes span two streams costs the host ~4-8 us per node to launch (tools/graph_launch_probe.py:
         64 nodes 211-245 us on two streams vs 50-58 us on one); with the step's ~70 nodes in one
         two-stream graph the host walk (~0.59 ms) paced the GPU and the side stream's kernels were
@@ -619,74 +620,48 @@ class FusedElboStep(object):
         e.handoff = None                     # the segments are joined by events between the graphs
         self.epi_adam.wait_flag = None
         self.epi_adam.wait_err = None
-        side = e._side_stream()
-        rom = bool(e.roms)
-        early = self.subset_early and rom
+        early = self.subset_early and bool(e.roms)
         e.side_pre = (lambda sst: self._launch_subset(sst, self.idx_next)) if early else None
-        n_enc = len(e.enc_descs) if e.ep is not None else 0
-        enc_split = bool(n_enc) and e.enc_reduce == 'split'
+        extra = {'forward_a': dict(zero_gacc=False, zero_scratch=False),
+                 'backward_side_a': dict(side_extra=lambda sst: self._launch_noise(
+                     sst, self.idx_next, codecs=('dec',), subset=not early))}
 
-        def cap(fn):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn(L.stream_handle())
-            return g
-
-        def m2(st):
-            e.forward_b(st)
-            e._running_pending = True            # running statistics deferred to the side stream
-            e.backward_a(st, rom)
-
-        def m5(st):
+        def tail(st):
             fused = self.fuse_adam
             if not fused:
                 L.check(L.lib().gpi_step_epilogue(C.byref(self.epi), st), 'step epilogue')
             self.allreduce()                     # RCCL: captured as a graph node
             self.update(st, fused=fused)
 
-        noise = (lambda sst: self._launch_noise(sst, self.idx_next, codecs=('dec',), subset=not early))
-        segs = {'m1': cap(lambda st: e.forward_a(st, zero_gacc=False, zero_scratch=False))}
-        if rom:
-            segs['s1'] = cap(e.rom_side)
-        segs['m2'] = cap(m2)
-        segs['s2'] = cap(lambda st: e.backward_side_a(st, rom, noise))
-        if n_enc:
-            segs['m3'] = cap(e.backward_b)
-        if enc_split:
-            segs['s3'] = cap(e.backward_side_b)
-        if n_enc:
-            segs['m4'] = cap(lambda st: e.backward_c(st, enc_split))
-        segs['m5'] = cap(m5)
-        self.segs = segs
-        self._seg_ev = [torch.cuda.Event() for _ in range(4)]
-        self._seg_side = side
+        def cap(seg):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                st = L.stream_handle()
+                for s in seg.rows:
+                    if s.piece is None:          # the main stream's continuation behind the side stream's end
+                        tail(st)
+                    else:
+                        getattr(e, s.piece)(st, **dict(s.args, **extra.get(s.piece, {})))
+            return g
+
+        # the table of the value not read after the forward and the BN running statistics deferred to the side
+        # stream; it has no rom_at / rom_first arm in this mode (ElboEngine.schedule)
+        self.segs = [(seg, cap(seg)) for seg in segments(e.schedule(False, 'defer', segments=True))]
+        self._seg_ev = {k: torch.cuda.Event() for k in (E_ROM, E_DEC, E_ENC, E_SIDE)}
+        self._seg_side = e._side_stream()
 
     def _replay_segments(self):
-        g, ev, side = self.segs, self._seg_ev, self._seg_side
-        main = torch.cuda.current_stream()
-        g['m1'].replay()
-        if 's1' in g:
-            ev[0].record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ev[0])
-                g['s1'].replay()
-        g['m2'].replay()
-        ev[1].record(main)
-        with torch.cuda.stream(side):
-            side.wait_event(ev[1])
-            g['s2'].replay()
-        if 'm3' in g:
-            g['m3'].replay()
-        if 's3' in g:
-            ev[2].record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ev[2])
-                g['s3'].replay()
-        ev[3].record(side)
-        if 'm4' in g:
-            g['m4'].replay()
-        main.wait_event(ev[3])
-        g['m5'].replay()
+        """The segment joiner's replay: the table's edges as events between the graphs."""
+        ev = self._seg_ev
+        streams = {MAIN: torch.cuda.current_stream(), SIDE: self._seg_side}
+        for seg, g in self.segs:
+            st = streams[seg.stream]
+            with torch.cuda.stream(st):
+                if seg.wait is not None:
+                    st.wait_event(ev[seg.wait])
+                g.replay()
+            if seg.signal is not None:
+                ev[seg.signal].record(st)
 
     def step(self):
         """One training step (graph replay once captured).  A timed-out cross-stream wait raises at a
@@ -790,7 +765,7 @@ class FusedElboStep(object):
         old = self.engine
         new = self._new_engine(flag)
         # the stream pair (probed hardware queues) and its events go with the step, not the engine
-        for k in ('_side', '_ev_fork', '_ev_join', '_ev_fork2', '_ev_join2', '_ev_enc', '_ev_start'):
+        for k in ('_side', '_ev'):
             if hasattr(old, k):
                 setattr(new, k, getattr(old, k))
         new.ws.t_flag.copy_(old.ws.t_flag)  # (the ROM's sticky conductivity flag: check_flag)

@@ -200,9 +200,11 @@ int env_int(const char* name, int dflt) {
     return v && *v ? atoi(v) : dflt;
 }
 
-// the decoder-likelihood epilogues: Gaussian (two channels: mean, logsigma) and Bernoulli (one channel: the logit)
+// the decoder-likelihood epilogues: Gaussian (two channels: mean, logsigma), Bernoulli (one channel: the logit) and
+// homoscedastic Gaussian (one channel: the mean; logsigma from the learned plane at ctx.ls_off)
 __host__ __device__ inline bool gauss_epi(int e) { return e == GPI_EPI_GAUSS_LOSS || e == GPI_EPI_GAUSS_EXP_LOSS; }
-__host__ __device__ inline bool loss_epi(int e) { return gauss_epi(e) || e == GPI_EPI_BERNOULLI_LOSS; }
+__host__ __device__ inline bool homo_epi(int e) { return e == GPI_EPI_GAUSS_HOMO_LOSS || e == GPI_EPI_GAUSS_HOMO_EXP_LOSS; }
+__host__ __device__ inline bool loss_epi(int e) { return gauss_epi(e) || homo_epi(e) || e == GPI_EPI_BERNOULLI_LOSS; }
 
 // NPX value of the forward's row-pair form (ConvGeom::npx, ShapeC::npxk): two vertically adjacent output
 // pixels x half of the output channels per thread
@@ -910,6 +912,19 @@ __device__ __forceinline__ void bern_px(float a, bool t, float scl, float& ll, f
     g = scl * (sig - (t ? 1.f : 0.f));
 }
 
+// Homoscedastic Gaussian log-likelihood of one pixel (GPI_EPI_GAUSS_HOMO_LOSS, ex: GPI_EPI_GAUSS_HOMO_EXP_LOSS): the
+// conv's mean mu, the pixel's log sigma ls from the learned plane, the target tgt -- the two-channel Gaussian
+// epilogue's arithmetic with ls read instead of computed.  gmu = d(-elbo)/d(mu), gls = this sample's d(-elbo)/d(ls).
+__device__ __forceinline__ void homo_px(float mu, float ls, float tgt, bool ex, float scl, float& ll, float& gmu,
+                                        float& gls) {
+    const float e = expf(-2.f * ls);
+    const float emu = ex ? expf(mu) : 1.f;
+    const float r = ex ? expf(tgt) - emu : tgt - mu;
+    ll = -0.5f * (2.f * ls + r * r * e + GPI_LOG2PI);
+    gmu = -scl * r * e * emu;
+    gls = scl * (1.f - r * r * e);
+}
+
 // ---------------------------------------------------------------------------------- forward
 // header floats: gst fp64 [4*MAX_CIN] | sc | sh [MAX_CIN] | scratch [64] | red [16] | dropout scales [8]
 constexpr int FWD_HDR = 8 * GPI_MAX_CIN + 2 * GPI_MAX_CIN + 64 + 16 + 8;
@@ -1021,6 +1036,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
     // the Bernoulli epilogue: the binary decoder's 5x5 / stride-1 output conv with one output channel (launch()
     // checks), so only that kernel's two-channel-slot instantiations carry it
     const bool bern = K == 5 && S == 1 && !UP && CP == 2 && d.epilogue == GPI_EPI_BERNOULLI_LOSS;
+    // the homoscedastic Gaussian epilogues: the same conv and instantiations (one mean channel; launch() checks)
+    const bool homo = K == 5 && S == 1 && !UP && CP == 2 && homo_epi(d.epilogue);
     if constexpr (NPX > 1) {
         constexpr int PADK = K / 2;   // launch() checks pad == k / 2
         // window column of tap kx of pixel p (x0 is a multiple of NPX, even, for the upsampling offsets)
@@ -1036,6 +1053,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
             for (int p = 0; p < NPX; ++p)
 #pragma unroll
                 for (int co = 0; co < CP; ++co) acc[p][co] = 0.f;
+            // homoscedastic epilogue: the pixels' log sigmas from the learned plane, in flight over the tap loop
+            float lsv[NPX];
+            if (homo) {
+#pragma unroll
+                for (int p = 0; p < NPX; ++p)
+                    lsv[p] = *as_gld(active ? params + c.ls_off + oy * d.w_out + x0 + p : zero);
+            }
             if (active && !SKIP(G, 64)) {
                 const int plane = Gt.rh * Gt.P;
                 const int cb = UP ? fdiv2(x0 - PADK) + HALO : x0 * S - PADK + HALO;
@@ -1109,6 +1133,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
                         Lv += ll;
                     }
                     store_px<NPX>(ws + d.gout_off + (int64_t)T.b * HWo + pix0, g0);      // one plane: [B][1][H][W]
+                    if (d.out_off >= 0)
+                        store_px<NPX>(ws + d.out_off + ((int64_t)T.b * d.out_ctot + d.out_c0) * HWo + pix0, m0);
+                }
+                continue;
+            }
+            if (homo) {
+                if (active) {
+                    int row = T.b - karg_sel(c.groups.start, T.grp);
+                    if (const int32_t* ti = karg_sel(c.tgt_idx, T.grp)) row = ti[row];
+                    const float* tg = karg_sel(c.tgt, T.grp) + (int64_t)row * HWo + pix0;
+                    const bool ex = d.epilogue == GPI_EPI_GAUSS_HOMO_EXP_LOSS;
+                    const float scl = karg_sel(c.loss_scale, T.grp);
+                    float g0[NPX], g1[NPX], m0[NPX];
+#pragma unroll
+                    for (int p = 0; p < NPX; ++p) {
+                        float ll;
+                        m0[p] = acc[p][0];
+                        homo_px(m0[p], lsv[p], tg[p], ex, scl, ll, g0[p], g1[p]);
+                        Lv += ll;
+                    }
+                    store_px<NPX>(ws + d.gout_off + (int64_t)T.b * HWo + pix0, g0);      // one plane: [B][1][H][W]
+                    // the sample's d/d(log sigma) row (summed over the batch by gpi_wgrad_reduce)
+                    if (c.gls_off >= 0) store_px<NPX>(c.wpart + c.gls_off + (int64_t)T.b * HWo + pix0, g1);
                     if (d.out_off >= 0)
                         store_px<NPX>(ws + d.out_off + ((int64_t)T.b * d.out_ctot + d.out_c0) * HWo + pix0, m0);
                 }
@@ -1335,11 +1382,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
             const int oy = T.oy0 + ty, ox = tx;
             bool active = pix < tp && grp < cg;
             float tgt = 0.f;
-            if ((gauss || bern) && active) {
+            if ((gauss || bern || homo) && active) {
                 int row = T.b - karg_sel(c.groups.start, T.grp);
                 if (const int32_t* ti = karg_sel(c.tgt_idx, T.grp)) row = ti[row];
                 tgt = karg_sel(c.tgt, T.grp)[(int64_t)row * HWo + oy * d.w_out + ox];
             }
+            // homoscedastic epilogue: the pixel's log sigma from the learned plane, loaded with the target
+            float lsp = 0.f;
+            if (homo && active) lsp = *as_gld(params + c.ls_off + oy * d.w_out + ox);
             PHASE(5);
             float acc[CP];
     #pragma unroll
@@ -1399,6 +1449,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
                 }
                 continue;
             }
+            if (homo) {
+                if (active) {
+                    float ll, gm, gs;
+                    homo_px(acc[0], lsp, tgt, d.epilogue == GPI_EPI_GAUSS_HOMO_EXP_LOSS, karg_sel(c.loss_scale, T.grp),
+                            ll, gm, gs);
+                    Lv += ll;
+                    const int64_t px = (int64_t)T.b * HWo + oy * d.w_out + ox;
+                    *as_gst(ws + d.gout_off + px) = gm;
+                    if (c.gls_off >= 0) *as_gst(c.wpart + c.gls_off + px) = gs;
+                    if (d.out_off >= 0)
+                        *as_gst(ws + d.out_off + (int64_t)T.b * d.out_ctot * HWo + (int64_t)d.out_c0 * HWo +
+                                oy * d.w_out + ox) = acc[0];
+                }
+                continue;
+            }
             if (gauss) {
                 if (active) {
                     const float mu = acc[0], ls = acc[1];
@@ -1438,7 +1503,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPX == 0 ? 
         }
     }
 
-    if (!ROWS2 && (gauss || bern)) {   // (fwd_rows2: never)
+    if (!ROWS2 && (gauss || bern || homo)) {   // (fwd_rows2: never)
         float v[1] = {Lv};
         block_sum<1>(v, scratch, red);      // thread 0 wrote red[0] itself: no barrier before reading it
         if (tid == 0 && !SKIP(G, 4)) atomicAdd(c.loss_acc + T.grp * GPI_REPLICAS + blockIdx.x % GPI_REPLICAS, (double)red[0]);
@@ -1527,7 +1592,8 @@ __device__ __forceinline__ float splat<float>(float v) { return v; }
 template <>
 __device__ __forceinline__ f32x2 splat<f32x2>(float v) { return f32x2{v, v}; }
 
-// EXF: the fused launch's loss form -- 0 Gaussian, 1 Gaussian of the exponentiated field, 2 Bernoulli (cout = 1)
+// EXF: the fused launch's loss form -- 0 Gaussian, 1 Gaussian of the exponentiated field, 2 Bernoulli (cout = 1),
+// 3 / 4 homoscedastic Gaussian of the log / exponentiated field (cout = 1, log sigma from the plane at ctx.ls_off)
 template <int K, int S, int UP, bool FUSE = false, bool HALF = false, int EXF = 0, int SHP = -1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (FUSE ? (SHP >= 0 ? GPI_FUSE_SHP_WAVES : GPI_FUSE_WAVES) : 4) : GPI_BWD_WAVES))) void conv_bwd_kernel(gpi_conv_desc d, gpi_codec_ctx c, ConvGeom G) {
     fold_shape<SHP>(d, G);
@@ -1623,7 +1689,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
         for (int e = tid; e < gimg / 4; e += 256) g4[e] = float4{0.f, 0.f, 0.f, 0.f};
     }
     const int CIV = d.cin <= 2 ? 2 : 4;      // vop: input channels per weight vector (zero padded)
-    constexpr int NCO = EXF == 2 ? 1 : 2;    // FUSE: output channels of the forward recompute (launch() checks cout)
+    constexpr int NCO = EXF >= 2 ? 1 : 2;    // FUSE: output channels of the forward recompute (launch() checks cout)
     if (vop) {
         // weights W[co][ci][ky][kx] transposed for the packed (v_pk_fma_f32) loops: input gradient
         // WB[((co K + ky) K + kx) CIV + ci]; FUSE forward WF[((ci K + kx) K + ky) NCO + co]
@@ -1904,11 +1970,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
         float Lv = 0.f;
         // the exp-field loss is an instantiation of its own (EXF; launch() picks it from d.epilogue): as a
         // runtime flag its two extra exps per pixel ran as selects in the log-field form as well
-        constexpr bool ex = EXF == 1;
+        constexpr bool ex = EXF == 1 || EXF == 4;
         // the Bernoulli form (EXF == 2): ONE channel, the logit -- a float accumulator and one FMA per tap, the
         // tap's weight by a broadcast ds_read_b32, and one plane of the gradient image
         constexpr bool bern = EXF == 2;
-        using acc_t = std::conditional_t<bern, float, f32x2>;
+        // the homoscedastic Gaussian forms (EXF == 3, 4): ONE channel as well, the mean; the pixel's log sigma is
+        // read from the learned plane, and the sample's d/d(log sigma) goes to its row of wpart (owned rows only:
+        // every (sample, pixel) is stored once, by the one workgroup that owns it, lanes along x)
+        constexpr bool homo = EXF == 3 || EXF == 4;
+        constexpr bool one_ch = bern || homo;
+        using acc_t = std::conditional_t<one_ch, float, f32x2>;
         const float scl = karg_sel(c.loss_scale, T.grp);
         const float xlo = bern ? karg_sel(c.tgt_lo, T.grp) : 0.f;
         // RPF vertically adjacent pixels of one column per thread: items (column, row group) fill the
@@ -1943,16 +2014,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                         tv[p] = it == tid ? tv0[p] : (ok ? as_gld(tg)[oy * d.w_out + x] : 0.f);
                     }
                 }
+                // homoscedastic forms: the item's log sigmas, in flight over the tap loop
+                float lsv[homo ? RPF : 1];
+                if constexpr (homo) {
+#pragma unroll
+                    for (int p = 0; p < RPF; ++p) {
+                        const int oy = gy0 + j0 + p;
+                        const bool ok = j0 + p < Gt.gh && oy >= 0 && oy < d.h_out;
+                        lsv[p] = *as_gld(ok ? params + c.ls_off + oy * d.w_out + x : zero);
+                    }
+                }
                 acc_t acc[RPF];
 #pragma unroll
                 for (int p = 0; p < RPF; ++p) acc[p] = splat<acc_t>(0.f);
-                // (Bernoulli form: one input channel per iteration -- unrolled over the channels the scheduler hoisted
-                // the LDS reads of several of them and spilled at the 5-wave budget)
-#pragma unroll(bern ? 1 : CIN)
+                // (one-channel forms: one input channel per iteration -- unrolled over the channels the scheduler hoisted
+                // the LDS reads of several of them and spilled at the 5-wave budget: 74-77 dwords in the
+                // homoscedastic forms)
+#pragma unroll(one_ch ? 1 : CIN)
                 for (int ci = 0; ci < CIN; ++ci) {
                     if (ci >= d.cin) break;
                     const float* acol = al + ci * Gt.rh * Gt.P + HALO + x - PADK;
-#pragma unroll(bern ? 1 : K)
+#pragma unroll(one_ch ? 1 : K)
                     for (int kx = 0; kx < K; ++kx) {
                         float v[RPF + K - 1];
 #pragma unroll
@@ -1986,6 +2068,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? (F
                         bern_px(acc[p], ((tb >> p) & 1u) != 0, scl, ll, gv);
                         if (own) Lv += ll;
                         g0[0] = gv;
+                    } else if constexpr (homo) {
+                        float ll, gm, gs;
+                        homo_px(acc[p], lsv[p], tv[p], ex, scl, ll, gm, gs);
+                        if (own) Lv += ll;
+                        g0[0] = gm;
+                        if (own && c.gls_off >= 0)
+                            *as_gst(c.wpart + c.gls_off + (int64_t)T.b * HWo + oy * d.w_out + x) = gs;
                     } else {
                         const float mu = acc[p][0], ls = acc[p][1];
                         const float e = expf(-2.f * ls);
@@ -2742,11 +2831,13 @@ conv_kernel_t pick(int cp, bool fwd, int npx, bool half, bool ucls = false) {
 }
 
 // fuse: the fused output conv's launch (launch() checks its shape: 5x5 / stride 1), exf its loss form (0 Gaussian,
-// 1 exponentiated-field Gaussian, 2 Bernoulli)
+// 1 exponentiated-field Gaussian, 2 Bernoulli, 3 / 4 homoscedastic Gaussian of the log / exponentiated field)
 conv_kernel_t select_kernel(const gpi_conv_desc& d, int cp, bool fwd, int npx, bool half, bool ucls, bool fuse,
                             int exf) {
     if (fuse) {
         if (exf == 2) return half ? conv_bwd_kernel<5, 1, 0, true, true, 2> : conv_bwd_kernel<5, 1, 0, true, false, 2>;
+        if (exf == 3) return half ? conv_bwd_kernel<5, 1, 0, true, true, 3> : conv_bwd_kernel<5, 1, 0, true, false, 3>;
+        if (exf == 4) return half ? conv_bwd_kernel<5, 1, 0, true, true, 4> : conv_bwd_kernel<5, 1, 0, true, false, 4>;
         if (half) return exf ? conv_bwd_kernel<5, 1, 0, true, true, 1> : conv_bwd_kernel<5, 1, 0, true, true>;
         return exf ? conv_bwd_kernel<5, 1, 0, true, false, 1> : conv_bwd_kernel<5, 1, 0, true>;
     }
@@ -2884,7 +2975,20 @@ int launch(const gpi_conv_desc& d, const gpi_codec_ctx& c, hipStream_t st, bool 
     if (bern && (fwd || fuse) && !dry)
         for (int g = 0; g < c.groups.n_groups; ++g)
             if (!c.tgt[g]) return GPI_ERR_ARG;
-    if (fuse && (fwd || d.k != 5 || d.stride != 1 || d.upsample || d.cout != (bern ? 1 : 2) || d.cin > 4 ||
+    // the homoscedastic Gaussian epilogues: one mean channel and a direct output gradient as well, the log-sigma
+    // plane among the parameters and, where the loss is computed, a target per group and (for the per-sample
+    // gradient rows) the slab buffer
+    const bool homo = homo_epi(d.epilogue);
+    if (homo && (d.cout != 1 || d.gout_mode != 1 || c.ls_off < 0)) return GPI_ERR_ARG;
+    if (homo && (d.k != 5 || d.stride != 1 || d.upsample)) return GPI_ERR_UNSUPPORTED;   // the decoder's output conv only
+    if (homo && (fwd || fuse) && !dry) {
+        for (int g = 0; g < c.groups.n_groups; ++g)
+            if (!c.tgt[g]) return GPI_ERR_ARG;
+        if (c.gls_off >= 0 && !c.wpart) return GPI_ERR_ARG;
+        // (the forward stores the rows as 16-byte vectors, like the images: aligned_ok's rule for them)
+        if (c.gls_off >= 0 && ((c.gls_off & 3) || ((uintptr_t)c.wpart & 15))) return GPI_ERR_UNSUPPORTED;
+    }
+    if (fuse && (fwd || d.k != 5 || d.stride != 1 || d.upsample || d.cout != (bern || homo ? 1 : 2) || d.cin > 4 ||
                  d.drop_off >= 0 || d.gout_mode != 1 || d.gin_off < 0 || !loss_epi(d.epilogue)))
         return GPI_ERR_UNSUPPORTED;
     if (gauss_epi(d.epilogue) && d.cout != 2) return GPI_ERR_ARG;
@@ -2893,7 +2997,8 @@ int launch(const gpi_conv_desc& d, const gpi_codec_ctx& c, hipStream_t st, bool 
     if (!fwd && d.gin_off >= 0 && ((G.ph * d.w_in) & 15)) return GPI_ERR_UNSUPPORTED;
     if (!fwd && d.gin_off >= 0 && d.stride == 2 && ((d.w_in & 7) || (G.ph & 1))) return GPI_ERR_UNSUPPORTED;
     const int cp = cp_of(d);
-    const int exf = bern ? 2 : d.epilogue == GPI_EPI_GAUSS_EXP_LOSS ? 1 : 0;
+    const int exf = bern ? 2 : homo ? (d.epilogue == GPI_EPI_GAUSS_HOMO_EXP_LOSS ? 4 : 3) :
+                    d.epilogue == GPI_EPI_GAUSS_EXP_LOSS ? 1 : 0;
     conv_kernel_t k = select_kernel(d, cp, fwd, G.cg > 1 ? 0 : G.npx, G.nfull < G.nblocks, G.ucls != 0, fuse, exf);
     if (!k) return GPI_ERR_UNSUPPORTED;
     static const float* zero = nullptr;

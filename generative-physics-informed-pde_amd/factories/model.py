@@ -7,7 +7,7 @@ encoder, dtype, device), with the reference's codec hyper-parameters.
 import torch
 
 from physics.LinearElliptic import LinearEllipticPhysics
-from bottleneck.Decoder import CNNDecoder
+from bottleneck.Decoder import CNNDecoder, HomoscedasticCNNDecoder
 from bottleneck.Encoder import CNNEncoder
 from bottleneck.components import EffectivePropertyMap, ReducedOrderModelOperator, PhysicsResolutionInterpolator
 from bottleneck.generative import GenerativeModel
@@ -90,9 +90,11 @@ class ModelFactory(object):
         physics = self._physics()
         c = self.CODEC
         n = p['nx_rom'] * 2 ** p['num_refines']
-        decoder = CNNDecoder(n, p['dim_latent'], (c['latent'], c['latent']), c['latent_features'], c['f_dec'],
-                             c['blocks'], p['binary_field'], c['growth'], drop_rate=p['droprate'],
-                             upsample='nearest', force_single_output=False, homoscedastic=p['homoscedastic'])
+        # homoscedastic=True (factories/model.py:231,253 of the reference): the decoder with the learned log-sigma plane
+        decoder_cls = HomoscedasticCNNDecoder if p['homoscedastic'] else CNNDecoder
+        decoder = decoder_cls(n, p['dim_latent'], (c['latent'], c['latent']), c['latent_features'], c['f_dec'],
+                              c['blocks'], p['binary_field'], c['growth'], drop_rate=p['droprate'],
+                              upsample='nearest', force_single_output=False, homoscedastic=p['homoscedastic'])
         encoder = CNNEncoder(n, p['dim_latent'], c['blocks'], c['growth'], c['f_enc'], drop_rate=p['droprate'])
         encoder = encoder.to(dtype=dtype, device=device)
         f = decoder.to(dtype=dtype, device=device)

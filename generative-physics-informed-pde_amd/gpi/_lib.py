@@ -28,6 +28,7 @@ FINALIZE_ACCUMULATE = 1
 FINALIZE_ZERO = 2
 
 EPI_STORE, EPI_STORE_STATS, EPI_GAUSS_LOSS, EPI_GAUSS_EXP_LOSS, EPI_BERNOULLI_LOSS = 0, 1, 2, 3, 4
+EPI_GAUSS_HOMO_LOSS, EPI_GAUSS_HOMO_EXP_LOSS = 5, 6
 HEAD_ENC, HEAD_REPARAM, HEAD_QZ, HEAD_LATENT, HEAD_GP, HEAD_LOCKX = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
 HEAD_PART_ENC, HEAD_PART_Q, HEAD_VALU = 0x100, 0x200, 0x400
 ROM_FORWARD, ROM_LOGLIK, ROM_BACKWARD = 0, 1, 2
@@ -78,7 +79,15 @@ class CodecCtx(C.Structure):
                 ('ext_in', vp), ('ext_idx', vp), ('ext_stride', i64),
                 ('tgt', vp * GPI_MAX_GROUPS), ('tgt_idx', vp * GPI_MAX_GROUPS),
                 ('loss_scale', f32 * GPI_MAX_GROUPS), ('tgt_lo', f32 * GPI_MAX_GROUPS), ('loss_acc', vp), ('n_stats', i64), ('bn_eps', f32),
-                ('groups', Groups)]
+                ('groups', Groups), ('ls_off', i64), ('gls_off', i64)]
+
+    def __init__(self, *a, **k):
+        # no homoscedastic log-sigma plane / gradient rows unless the caller sets them
+        super().__init__(*a, **k)
+        if 'ls_off' not in k:
+            self.ls_off = -1
+        if 'gls_off' not in k:
+            self.gls_off = -1
 
 
 class ReduceItem(C.Structure):

@@ -449,10 +449,17 @@ class ElboEngine(object):
         # the decoder likelihood of generative.py:232-244: log-property Gaussian (default) or the
         # exponentiated field's (reconstruct_log_eff_property = False); a binary decoder (one logit channel)
         # takes the Bernoulli likelihood whatever that option says -- the reference tests the prediction's
-        # type first
+        # type first.  A homoscedastic decoder (one mean channel + the learned log-sigma plane f.logsigma,
+        # Decoder.py:204-212,271-285) takes the same Gaussian of either field with log sigma read from the plane
         log_field = getattr(model, 'config', {}).get('reconstruct_log_eff_property', True)
         self.binary = bool(getattr(dec, '_binary', False))
-        epi = L.EPI_BERNOULLI_LOSS if self.binary else (L.EPI_GAUSS_LOSS if log_field else L.EPI_GAUSS_EXP_LOSS)
+        self.homosc = bool(getattr(dec, '_homoscedastic', False)) and not self.binary
+        if self.binary:
+            epi = L.EPI_BERNOULLI_LOSS
+        elif self.homosc:
+            epi = L.EPI_GAUSS_HOMO_LOSS if log_field else L.EPI_GAUSS_HOMO_EXP_LOSS
+        else:
+            epi = L.EPI_GAUSS_LOSS if log_field else L.EPI_GAUSS_EXP_LOSS
         self.dp = decoder_program(final_epilogue=epi, **dc)
         self.dec_sizes = [n for n in (self.B_u, self.N_s, self.N_vo) if n > 0]
         self.g_sup = (1 if self.B_u > 0 else 0) if self.N_s > 0 else None
@@ -504,6 +511,12 @@ class ElboEngine(object):
         for key, n in (('sup', self.N_s), ('vo', 0 if self.vo_holdoff else self.N_vo)):
             if n > 0:
                 self.gls_off[key] = ws.parts.alloc(n * self.d_y)
+        # homoscedastic decoder: the per-sample d/dlogsigma rows [B][H W] of the plane, written by the loss
+        # epilogue and summed over the batch with the decoder slabs; none without shared_grads (the plane is read,
+        # its gradient never formed)
+        self.dec_gls_off = -1
+        if self.homosc and self.shared_grads:
+            self.dec_gls_off = ws.parts.alloc(self.B * self.dp.output.per_sample)
         ws.materialize(flat.P.device)
         su = 1.0 / self.B_u if (self.normalize and self.B_u) else 1.0
         ss = 1.0 / self.N_s if (self.normalize and self.N_s) else 1.0
@@ -516,6 +529,9 @@ class ElboEngine(object):
         self.dctx = make_ctx(ws, flat, self.dec_sizes)
         for gi, scale in enumerate([su] * (self.B_u > 0) + [ss] * (self.N_s > 0) + [sv] * (self.N_vo > 0)):
             self.dctx.loss_scale[gi] = scale
+        if self.homosc:
+            self.dctx.ls_off = flat.offset(dec.logsigma)
+            self.dctx.gls_off = self.dec_gls_off
 
     def _build_head(self):
         """The dense head's descriptor (head) and the MLP effective-property map's (gpm, or None)."""
@@ -677,6 +693,13 @@ class ElboEngine(object):
             self.roms.append(self.rom_vo)
         # the ROMs' d/dlogsigma_y rows are reduced with the decoder slabs (after the ROMs on the side stream)
         dec_items = self.dp.reduce_items(lambda n: self._poff(self.dec, n)) if self.shared_grads else []
+        if self.dec_gls_off >= 0:
+            # the homoscedastic plane's gradient: the cross-batch sum of the epilogue's per-sample rows
+            it = L.ReduceItem()
+            hw = self.dp.output.per_sample
+            it.part_off, it.w_off, it.numel, it.row_stride, it.blocks = (self.dec_gls_off, flat.offset(self.dec.logsigma),
+                                                                         hw, hw, self.B)
+            dec_items.append(it)
         self.reduce_dec = dec_items + self.rom_reduce
         self.reduce_items = self.reduce_enc + self.reduce_dec
 

@@ -111,7 +111,9 @@ class EvalEncoderEngine(object):
 
 class EvalDecoderEngine(object):
     """CNNDecoder.forward in eval mode: z -> (mean, logsigma) [B, 2, H, W], or the probability image
-    [B, 1, H, W] of a binary decoder (the sigmoid of the kernels' logit image); forward only."""
+    [B, 1, H, W] of a binary decoder (the sigmoid of the kernels' logit image), or the mean image
+    [B, 1, H, W] of a homoscedastic decoder (CNNDecoder.forward expands its log-sigma plane beside it, on the
+    host side: the plane is a parameter, not a kernel output); forward only."""
     mode = 'eval'
 
     def __init__(self, dec, flat, B):

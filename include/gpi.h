@@ -62,6 +62,15 @@ extern "C" {
                                      in the logit form (-softplus(-a) if t else -softplus(a)), writes
                                      d(-elbo)/d(a) = loss_scale (sigmoid(a) - t); the binary CNNDecoder
                                      (Decoder.py:204-207, generative.py:232-244) */
+#define GPI_EPI_GAUSS_HOMO_LOSS 5 /* cout == 1: the conv output is the mean; log sigma of pixel (oy, ox) is the learned plane
+                                     params[ctx->ls_off + oy W + ox], the same for every sample and group (the
+                                     homoscedastic CNNDecoder, Decoder.py:204-212,271-285, scored by the diagonal Gaussian of
+                                     generative.py:232-239).  ll = -1/2 (2 ls + r^2 exp(-2 ls) + log 2 pi), r = target - mean;
+                                     writes d(-elbo)/d(mean) = -loss_scale r exp(-2 ls) into the one gradient plane
+                                     [B][1][H][W] and, when ctx->gls_off >= 0, the sample's d(-elbo)/d(ls) row
+                                     loss_scale (1 - r^2 exp(-2 ls)) to wpart[ctx->gls_off + b H W + oy W + ox] */
+#define GPI_EPI_GAUSS_HOMO_EXP_LOSS 6  /* as GAUSS_HOMO_LOSS on the exponentiated field: r = exp(target) - exp(mean), the mean
+                                          gradient carries the factor exp(mean) (generative.py:238-239) */
 
 /* Per-channel BatchNorm statistics record, one per (channel, group). */
 typedef struct gpi_stat {
@@ -133,6 +142,12 @@ typedef struct gpi_codec_ctx {
     int64_t n_stats;               /* stat records per replica */
     float bn_eps;                  /* 1e-5 (torch default) */
     gpi_groups groups;
+    /* the homoscedastic decoder's learned log-sigma plane [H][W] (Decoder.py:204-212,271-285; generative.py:232-239),
+     * read by GPI_EPI_GAUSS_HOMO_LOSS / GPI_EPI_GAUSS_HOMO_EXP_LOSS only */
+    int64_t ls_off;                /* parameter offset of the plane; < 0 with one of those epilogues: GPI_ERR_ARG */
+    int64_t gls_off;               /* float offset into wpart of the per-sample gradient rows [B][H W] (summed over the
+                                      batch by one gpi_reduce_item: blocks = B, numel = row_stride = H W); < 0: the rows
+                                      are not written (input-gradient-only callers) */
 } gpi_codec_ctx;
 
 /* Slab reduction item: gacc[w_off + i] += sum_b wpart[part_off + b*row_stride + i], i < numel. */
@@ -673,7 +688,9 @@ int gpi_conv_backward(const gpi_conv_desc* op, const gpi_codec_ctx* ctx, void* s
  * output gradient never leaves LDS).  op: k = 5, stride 1, no upsampling, cin <= 4, cout = 2,
  * epilogue GPI_EPI_GAUSS_LOSS / GPI_EPI_GAUSS_EXP_LOSS, gout_mode 1, no dropout; out_off is ignored.
  * With epilogue GPI_EPI_BERNOULLI_LOSS the op has cout = 1 (the binary decoder's logit) and the launch is the
- * kernel's one-channel instantiation: one forward accumulator and one gradient plane per pixel. */
+ * kernel's one-channel instantiation: one forward accumulator and one gradient plane per pixel; so it is with
+ * GPI_EPI_GAUSS_HOMO_LOSS / GPI_EPI_GAUSS_HOMO_EXP_LOSS (cout = 1: the mean), which also stores each owned
+ * pixel's log-sigma gradient to the sample's row at ctx->gls_off (once, by the tile that owns the pixel). */
 int gpi_conv_loss_fused(const gpi_conv_desc* op, const gpi_codec_ctx* ctx, void* stream);
 /* Run a codec program: ops in order (forward) / reverse order (backward). */
 int gpi_codec_forward(const gpi_conv_desc* ops, int n_ops, const gpi_codec_ctx* ctx, void* stream);

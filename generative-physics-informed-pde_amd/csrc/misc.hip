@@ -16,11 +16,29 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(double* __restrict__
     if (flags & GPI_FINALIZE_ZERO) gacc[i] = 0.0;
 }
 
+// The step's L2 penalty (gpi_param_norms): its fp32 gradient joins the finalised fp32 gradient of -ELBO, never the
+// fp64 accumulator (whose order-independence rests on fp32-valued partials); elements outside the penalised
+// segments hold 0 in pen_grad and keep their bits (the sign of a zero gradient included).
+__device__ __forceinline__ float with_penalty(float g, const gpi_step_epilogue_desc& d, int64_t i) {
+    if (i < d.pen_n) {
+        const float pg = d.pen_grad[i];
+        if (pg != 0.f) g += pg;
+    }
+    return g;
+}
+
+__device__ __forceinline__ void save_penalty(const gpi_step_epilogue_desc& d) {   // one thread of the launch
+    if (d.pen_src) {
+        d.pen_dst[0] = d.pen_src[0];
+        d.pen_dst[1] = d.pen_src[1];
+    }
+}
+
 __global__ __launch_bounds__(256) void step_epilogue_kernel(gpi_step_epilogue_desc d) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (d.step && i == 0) *d.step += 1;
     if (i < d.n) {
-        float g = (float)d.gacc[i];
+        float g = with_penalty((float)d.gacc[i], d, i);
         // the data-parallel error slot: this rank's hand-off timeout, summed over the ranks by the all-reduce
         if (i == d.err_slot && d.wait_err && __hip_atomic_load(d.wait_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
             g = 1.f;
@@ -32,6 +50,7 @@ __global__ __launch_bounds__(256) void step_epilogue_kernel(gpi_step_epilogue_de
         d.scratch[i] = 0.0;
     }
     if (i < d.n_idx) d.idx_dst[i] = d.idx_src[i];
+    if (i == 0) save_penalty(d);
     if (i * 4 < d.drop_n) {                      // gpi_dropout_masks' draw, Philox block i
         const uint64_t base = d.drop_offset ? *d.drop_offset : 0;
         const uint4_ r = philox(base + (uint64_t)i, d.drop_sub, d.drop_seed);
@@ -81,10 +100,11 @@ __global__ __launch_bounds__(256) void step_epilogue_adam_kernel(gpi_step_epilog
     const float step_size = (float)((double)lr / bc1);
     const float bc2_sqrt = (float)sqrt(bc2);
     const float scale = 1.f / (1.f - d.drop_p);
+    if (blockIdx.x == 0 && threadIdx.x == 0) save_penalty(d);
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m_items; i += stride) {
         if (i < d.n) {
-            const float g = (float)d.gacc[i];
+            const float g = with_penalty((float)d.gacc[i], d, i);
             d.grad[i] = g;
             d.gacc[i] = 0.0;
             if (!skip) {
@@ -138,8 +158,12 @@ __global__ __launch_bounds__(256) void adam_kernel(gpi_adam_desc d) {
     const float step_size = (float)((double)lr / bc1);
     const float bc2_sqrt = (float)sqrt(bc2);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < d.n; i += (int64_t)gridDim.x * 256) {
-        float p = d.p[i], m = d.m[i], v = d.v[i];
-        adam_element(d.g[i], p, m, v, d.beta1, d.beta2, d.eps, step_size, bc2_sqrt);
+        float p = d.p[i], m = d.m[i], v = d.v[i], g = d.g[i];
+        if (i < d.pen_n) {                      // the L2 penalty of a data-parallel step: after the all-reduce
+            const float pg = d.pen_grad[i];
+            if (pg != 0.f) d.g[i] = g = g + pg;
+        }
+        adam_element(g, p, m, v, d.beta1, d.beta2, d.eps, step_size, bc2_sqrt);
         d.m[i] = m;
         d.v[i] = v;
         d.p[i] = p;
@@ -410,7 +434,90 @@ __global__ void queue_probe_kernel(const uint32_t* flag, uint32_t* seen) {
     __hip_atomic_store(seen, ok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// gpi_param_norms: workgroup s owns segment s of the flat parameter buffer.  Pass 1: lane t adds the squares of
+// elements t, t + 1024, ... in that order (a product of two fp32 values is exact in fp64), the butterfly leaves every
+// lane of a wave the same sum, the 16 wave sums are added in wave order: the same bits on every launch.  Pass 2
+// (the segment's lines are in L2 by now): the gradient lambda p / ||p||, rounded once.  The segment sum goes through
+// the arrival counter: each workgroup stores its norm write-through (an agent-scope atomic store), drains it and
+// adds to the counter; the last arriver reads all norms past its L1 (agent-scope atomic loads) and adds them in
+// segment order.  One LDS array serves the wave sums, the "I am last" word and the norms' staging.
+constexpr int PN_THREADS = 1024;
+
+__global__ __launch_bounds__(PN_THREADS) void param_norms_kernel(gpi_param_norms_desc d) {
+    __shared__ double sh[PN_THREADS];
+    const int s = blockIdx.x, t = threadIdx.x;
+    const int64_t off = d.seg[2 * s], n = d.seg[2 * s + 1];
+    // (the launcher refuses such a table from its host copy; a device table that differs from it is skipped)
+    const bool ok = off >= 0 && n >= 1 && n <= d.pen_n && off <= d.pen_n - n;
+    const float* p = d.p + (ok ? off : 0);
+    const int64_t cnt = ok ? n : 0;
+    double acc = 0.0;
+    int64_t i = t;
+    for (; i + 3 * PN_THREADS < cnt; i += 4 * PN_THREADS) {     // four loads in flight, added in index order
+        const double a = p[i], b = p[i + PN_THREADS], c = p[i + 2 * PN_THREADS], e = p[i + 3 * PN_THREADS];
+        acc = fma(a, a, acc);
+        acc = fma(b, b, acc);
+        acc = fma(c, c, acc);
+        acc = fma(e, e, acc);
+    }
+    for (; i < cnt; i += PN_THREADS) {
+        const double a = p[i];
+        acc = fma(a, a, acc);
+    }
+    acc = wave_sum_d(acc);
+    if ((t & 63) == 0) sh[t >> 6] = acc;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < PN_THREADS / 64; ++w) tot += sh[w];
+    const double norm = ok ? sqrt(tot) : __builtin_nan("");
+    // torch.norm's backward at a zero tensor is 0 (a NaN norm keeps its NaN)
+    const double coef = norm == 0.0 ? 0.0 : (double)*d.lambda / norm;
+    for (i = t; i < cnt; i += PN_THREADS) d.pen_grad[off + i] = norm == 0.0 ? 0.f : (float)((double)p[i] * coef);
+    __syncthreads();                                            // every thread has read the wave sums
+    if (t == 0) {
+        __hip_atomic_store(d.norms + s, norm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the norm is out before the arrival counts it
+        const uint32_t prev = __hip_atomic_fetch_add(d.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sh[0] = prev == gridDim.x - 1 ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const bool last = sh[0] != 0.0;
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // (no instruction: the loads below stay below)
+    double pen = 0.0;
+    for (int base = 0; base < d.n_seg; base += PN_THREADS) {
+        if (base + t < d.n_seg)
+            sh[t] = __hip_atomic_load(d.norms + base + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (t == 0) {
+            const int m = d.n_seg - base < PN_THREADS ? d.n_seg - base : PN_THREADS;
+            for (int j = 0; j < m; ++j) pen += sh[j];           // segment order
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        d.pen[0] = pen;
+        d.pen[1] = (double)*d.lambda * pen;
+        __hip_atomic_store(d.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 }  // namespace
+
+extern "C" int gpi_param_norms(const gpi_param_norms_desc* d, void* stream) {
+    if (!d || d->n_seg <= 0 || d->pen_n <= 0) return GPI_ERR_ARG;
+    if (!d->p || !d->seg || !d->seg_host || !d->lambda || !d->norms || !d->pen || !d->pen_grad || !d->done)
+        return GPI_ERR_ARG;
+    for (int s = 0; s < d->n_seg; ++s) {
+        const int64_t off = d->seg_host[2 * s], n = d->seg_host[2 * s + 1];
+        if (off < 0 || n < 1 || n > d->pen_n || off > d->pen_n - n) return GPI_ERR_ARG;
+    }
+    hipLaunchKernelGGL(param_norms_kernel, dim3((unsigned)d->n_seg), dim3(PN_THREADS), 0, (hipStream_t)stream, *d);
+    GPI_CHECK_LAUNCH();
+    return GPI_OK;
+}
 
 extern "C" int gpi_queue_probe(const uint32_t* flag, uint32_t* seen, void* stream) {
     if (!flag || !seen) return GPI_ERR_ARG;
@@ -524,7 +631,8 @@ extern "C" int gpi_struct_sizes(int64_t* out, int n) {
                          (int64_t)sizeof(gpi_vo_sparse), (int64_t)sizeof(gpi_draw_item),
                          (int64_t)sizeof(gpi_bn_exchange_desc), (int64_t)sizeof(gpi_bn_eval_item),
                          (int64_t)sizeof(gpi_vo_energy_desc), (int64_t)sizeof(gpi_rom_fit_desc),
-                         (int64_t)sizeof(gpi_gpmlp_desc), (int64_t)sizeof(gpi_gpmlp_sample_desc)};
+                         (int64_t)sizeof(gpi_gpmlp_desc), (int64_t)sizeof(gpi_gpmlp_sample_desc),
+                         (int64_t)sizeof(gpi_param_norms_desc)};
     const int k = (int)(sizeof(s) / sizeof(s[0]));
     if (!out || n < k) return GPI_ERR_ARG;
     for (int i = 0; i < k; ++i) out[i] = s[i];
@@ -556,6 +664,7 @@ extern "C" int gpi_step_epilogue(const gpi_step_epilogue_desc* d, void* stream) 
         (d->n_idx && (!d->idx_src || !d->idx_dst)))
         return GPI_ERR_ARG;
     if (d->drop_n < 0 || (d->drop_n && (!d->drop_out || !(d->drop_p >= 0.f && d->drop_p < 1.f)))) return GPI_ERR_ARG;
+    if (d->pen_n < 0 || d->pen_n > d->n || (d->pen_n && !d->pen_grad) || (d->pen_src && !d->pen_dst)) return GPI_ERR_ARG;
     int64_t m = d->n > d->n_scratch ? d->n : d->n_scratch;
     if (d->n_idx > m) m = d->n_idx;
     if ((d->drop_n + 3) / 4 > m) m = (d->drop_n + 3) / 4;
@@ -573,10 +682,11 @@ extern "C" int gpi_step_epilogue_adam(const gpi_step_epilogue_desc* d, const gpi
         (d->n_idx && (!d->idx_src || !d->idx_dst)))
         return GPI_ERR_ARG;
     if (d->drop_n < 0 || (d->drop_n && (!d->drop_out || !(d->drop_p >= 0.f && d->drop_p < 1.f)))) return GPI_ERR_ARG;
+    if (d->pen_n < 0 || d->pen_n > d->n || (d->pen_n && !d->pen_grad) || (d->pen_src && !d->pen_dst)) return GPI_ERR_ARG;
     // the fused form owns the counter (Adam's) and always zeroes the accumulator; the update covers
     // exactly the gradient's elements
     if (d->flags != GPI_FINALIZE_ZERO || d->step || !a->p || !a->g || !a->m || !a->v || !a->lr || !a->step ||
-        a->n != d->n || a->g != d->grad || (d->drop_n && d->drop_offset && a->rng_offset &&
+        a->n != d->n || a->g != d->grad || a->pen_n != 0 || (d->drop_n && d->drop_offset && a->rng_offset &&
                                               d->drop_offset != a->rng_offset))
         return GPI_ERR_ARG;
     int64_t m = d->n > d->n_scratch ? d->n : d->n_scratch;
@@ -592,6 +702,7 @@ extern "C" int gpi_step_epilogue_adam(const gpi_step_epilogue_desc* d, const gpi
 
 extern "C" int gpi_adam(const gpi_adam_desc* d, void* stream) {
     if (!d || !d->p || !d->g || !d->m || !d->v || !d->lr || !d->step || d->n < 0) return GPI_ERR_ARG;
+    if (d->pen_n < 0 || d->pen_n > d->n || (d->pen_n && !d->pen_grad)) return GPI_ERR_ARG;
     if (d->n == 0) return GPI_OK;
     int64_t nb = (d->n + 255) / 256;
     if (nb > 2048) nb = 2048;

@@ -139,7 +139,7 @@ class ResidualDesc(C.Structure):
 class AdamDesc(C.Structure):
     _fields_ = [('p', vp), ('g', vp), ('m', vp), ('v', vp), ('n', i64), ('lr', vp), ('step', vp),
                 ('beta1', f32), ('beta2', f32), ('eps', f32), ('_pad', f32), ('rng_offset', vp),
-                ('rng_advance', C.c_uint64), ('wait_err', vp), ('skip_if', vp)]
+                ('rng_advance', C.c_uint64), ('wait_err', vp), ('skip_if', vp), ('pen_grad', vp), ('pen_n', i64)]
 
 
 class VoQueryDesc(C.Structure):
@@ -220,7 +220,7 @@ class StepEpilogueDesc(C.Structure):
                 ('scratch', vp), ('n_scratch', i64), ('terms_dst', vp), ('idx_src', vp), ('idx_dst', vp),
                 ('n_idx', i64), ('drop_out', vp), ('drop_n', i64), ('drop_p', f32), ('_pad2', i32),
                 ('drop_seed', u64), ('drop_offset', vp), ('drop_sub', u64), ('wait_flag', vp), ('wait_err', vp),
-                ('err_slot', i64)]
+                ('err_slot', i64), ('pen_grad', vp), ('pen_n', i64), ('pen_src', vp), ('pen_dst', vp)]
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
@@ -258,10 +258,15 @@ class BnExchangeDesc(C.Structure):
                 ('peer_buf', vp * GPI_MAX_RANKS), ('peer_flag', vp * GPI_MAX_RANKS), ('seq', vp), ('err', vp)]
 
 
+class ParamNormsDesc(C.Structure):
+    _fields_ = [('p', vp), ('seg', vp), ('seg_host', vp), ('n_seg', i32), ('_pad', i32), ('pen_n', i64),
+                ('lam', vp), ('norms', vp), ('pen', vp), ('pen_grad', vp), ('done', vp)]
+
+
 STRUCTS = [Stat, Groups, ConvDesc, CodecCtx, ReduceItem, HeadDesc, GemmItem, RomDesc, ResidualDesc, AdamDesc,
            VoQueryDesc, VoMomentsDesc, VoConditionDesc, VoPrecisionDesc, GpSampleDesc,
            VoGalerkinDesc, StepEpilogueDesc, FomDesc, RandomFieldDesc, VoSparse, DrawItem, BnExchangeDesc,
-           BnEvalItem, VoEnergyDesc, RomFitDesc, GpMlpDesc, GpMlpSampleDesc]
+           BnEvalItem, VoEnergyDesc, RomFitDesc, GpMlpDesc, GpMlpSampleDesc, ParamNormsDesc]
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -335,6 +340,7 @@ SIGNATURES = {
     'gpi_gpmlp_forward': (C.c_int, [C.POINTER(GpMlpDesc), vp, vp, vp]),
     'gpi_gpmlp_backward': (C.c_int, [C.POINTER(GpMlpDesc), vp, vp, vp, vp]),
     'gpi_gpmlp_sample': (C.c_int, [C.POINTER(GpMlpSampleDesc), vp]),
+    'gpi_param_norms': (C.c_int, [C.POINTER(ParamNormsDesc), vp]),
 }
 
 _LIB = None

@@ -49,6 +49,23 @@ def allreduce_shared(flat, group=None):
         dist.all_reduce(flat.G[:n], op=dist.ReduceOp.SUM, group=group)
 
 
+def l2_segments(model, flat=None):
+    """The tensors model.elbo(l2_penalty=) penalises (generative.py:381-385: f.parameters(), then
+    encoder.parameters() when the model has an encoder) as rows (name, offset, numel) of the flat parameter
+    buffer, in that order.  No device work."""
+    flat = flat if flat is not None else model.native_flat()
+    rows = []
+    for prefix, mod in (('f.', model.f), ('encoder.', getattr(model, 'encoder', None))):
+        if mod is not None:
+            rows += [(prefix + n, flat.offset(p), p.numel()) for n, p in mod.named_parameters()]
+    return rows
+
+
+def param_norms(desc, stream):
+    """One gpi_param_norms launch (the fused step's only call site of the entry point)."""
+    L.check(L.lib().gpi_param_norms(C.byref(desc), stream), 'parameter norms')
+
+
 class FusedAdamSchedule(torch.optim.Optimizer):
     """The learning-rate handle of a FusedElboStep as a torch Optimizer, so that torch LR schedulers
     (and lamp.optimization.LearningScheduleWrapper, lamp/optimization.py:71-93, training.py:452,615)
@@ -74,12 +91,22 @@ class FusedElboStep(object):
     launch against targets y ~ N(vo.mean, vo.var), drawn with the step's other noise from the ensemble's
     persistent fp32 buffers (``vo``: model.VO, either ensemble family).  vo_holdoff: the term's logL_x - KL
     part only (training.py:411); set_vo_holdoff switches.  update_virtual_observables is the loop's VO
-    update (training.py:407-409)."""
+    update (training.py:407-409).
+
+    l2_penalty: model.elbo's l2_penalty (generative.py:381-385) in the step.  None (the default): no penalty and
+    no launch for it.  A number, 0.0 included: elbo() loses l2_penalty * sum of the 2-norms of the decoder's and
+    the encoder's parameter tensors (l2_segments; not divided under normalize=True, as in the reference), the
+    gradient gains the penalty's, terms() the reference's 'elbo_l2_penalty'.  One gpi_param_norms launch per step
+    on the side stream, beside the next step's noise draws; its fp32 gradient is added where the gradient is
+    finalised (the step epilogue).  ``l2`` is a device scalar: set_l2_penalty edits it between steps, captured or
+    not.  Data parallel: every rank computes the norms and adds the penalty's gradient to the all-reduced
+    gradient after the SUM (in the Adam launch, which stores the sum back into flat.G), so it enters once; rank 0
+    alone subtracts the penalty in elbo(), so the ranks' values sum to the global objective."""
 
     def __init__(self, model, X_pool, B_u, X_s=None, Y=None, F=None, lr=1e-2, betas=(0.9, 0.999), eps=1e-8,
                  seed=0, normalize=False, process_group=None, distributed=False, rank=0, world=1, subset_seed=None,
                  graph_allreduce=True, sync_bn=False, bn_exchange='collective', X_vo=None, F_vo=None, vo=None,
-                 vo_holdoff=False):
+                 vo_holdoff=False, l2_penalty=None):
         self.model = model
         self.N_s = 0 if X_s is None else int(X_s.shape[0])
         self.N_vo = 0 if X_vo is None else int(X_vo.shape[0])
@@ -190,6 +217,9 @@ class FusedElboStep(object):
         self.adam.rng_offset = self.rng_off.data_ptr()
         self.adam.rng_advance = self.rng_span
         self.last_terms = torch.zeros(L.GPI_REPLICAS * 16, dtype=torch.float64, device=dev)
+        self.l2 = None
+        if l2_penalty is not None:
+            self._build_l2(float(l2_penalty))
         # single-process steps: the epilogue and Adam in one launch (gpi_step_epilogue_adam; nothing
         # runs between the gradient delivery and the update); GPI_FUSED_ADAM=0 keeps two launches
         self.fuse_adam = not self.distributed and os.environ.get('GPI_FUSED_ADAM', '1') != '0'
@@ -252,6 +282,45 @@ class FusedElboStep(object):
         else:
             engine.bind(X_u=self.X_pool, u_index=my_idx, X_s=self.X_s, Y=self.Y, F=self.F)
 
+    def _build_l2(self, l2_penalty):
+        """The penalty's buffers and its launch descriptor.  pen_grad is dense over the flat prefix that holds
+        the penalised tensors and is written at their elements only: the zeros between them stay."""
+        dev = self.flat.P.device
+        rows = l2_segments(self.model, self.flat)
+        if not rows:
+            raise ValueError('FusedElboStep: l2_penalty without a parameter to penalise')
+        table = [v for _, o, n in rows for v in (o, n)]
+        self.pen_n = max(o + n for _, o, n in rows)
+        assert self.pen_n <= self.flat.n_shared
+        self._l2_seg_host = (C.c_int64 * len(table))(*table)
+        self.l2_seg = torch.tensor(table, dtype=torch.int64, device=dev)
+        self.l2 = torch.tensor([l2_penalty], dtype=torch.float32, device=dev)
+        self.pen_grad = torch.zeros(self.pen_n, dtype=torch.float32, device=dev)
+        self.l2_norms = torch.zeros(len(rows), dtype=torch.float64, device=dev)
+        self.l2_pen = torch.zeros(2, dtype=torch.float64, device=dev)      # {pen, l2 * pen} of the running step
+        self.last_pen = torch.zeros(2, dtype=torch.float64, device=dev)    # ... of the last completed step
+        self.l2_done = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.norms_desc = L.ParamNormsDesc(p=self.flat.P.data_ptr(), seg=self.l2_seg.data_ptr(),
+                                           seg_host=C.addressof(self._l2_seg_host), n_seg=len(rows),
+                                           pen_n=self.pen_n, lam=self.l2.data_ptr(), norms=self.l2_norms.data_ptr(),
+                                           pen=self.l2_pen.data_ptr(), pen_grad=self.pen_grad.data_ptr(),
+                                           done=self.l2_done.data_ptr())
+
+    def set_l2_penalty(self, value):
+        """Change the penalty's factor in place (an async fill, valid between steps; a captured step reads the
+        device scalar).  Switching between None and a number needs a new step."""
+        if self.l2 is None:
+            raise L.NativeError('FusedElboStep.set_l2_penalty: the step was built with l2_penalty=None')
+        self.l2.fill_(float(value))
+
+    def _side_extra(self, sst, early):
+        """The side stream's extra work of a step, concurrent with the encoder backward: the next step's noise
+        and, with an L2 penalty, this step's parameter norms -- the parameters are written by Adam alone, at the
+        step's end, behind the epilogue's join with this stream."""
+        self._launch_noise(sst, self.idx_next, codecs=('dec',), subset=not early)
+        if self.l2 is not None:
+            param_norms(self.norms_desc, sst)
+
     def _build_epilogue(self):
         """The epilogue descriptors over the current engine's scratch and encoder masks."""
         ws = self.engine.ws
@@ -271,6 +340,18 @@ class FusedElboStep(object):
             self.epi.drop_seed = self.seed
             self.epi.drop_offset = self.rng_off.data_ptr()
             self.epi.drop_sub = 4
+        if self.l2 is not None:
+            self.epi.pen_src = self.l2_pen.data_ptr()
+            self.epi.pen_dst = self.last_pen.data_ptr()
+            if self.distributed:
+                # data parallel: into the all-reduced gradient, once on every rank, by the Adam launch (ahead of
+                # the SUM it would count `world` times; on one rank alone it would be rounded into that rank's
+                # partial gradient, which can be far larger than the sum)
+                self.adam.pen_grad = self.pen_grad.data_ptr()
+                self.adam.pen_n = self.pen_n
+            else:
+                self.epi.pen_grad = self.pen_grad.data_ptr()
+                self.epi.pen_n = self.pen_n
         self.epi_adam = L.StepEpilogueDesc.from_buffer_copy(self.epi)
         self.epi_adam.step = None                  # Adam's counter: incremented once by the fused launch
 
@@ -391,8 +472,7 @@ class FusedElboStep(object):
         # encoder's masks by the epilogue below (the encoder backward reads this step's)
         # the fused epilogue + Adam launch (update(fused=True)) waits for the side stream itself; every
         # other continuation needs the main stream to wait here
-        self.engine.backward(st, side_extra=lambda sst: self._launch_noise(sst, self.idx_next, codecs=('dec',),
-                                                                           subset=not early),
+        self.engine.backward(st, side_extra=lambda sst: self._side_extra(sst, early),
                              main_wait=epilogue or not self.fuse_adam)
         if epilogue:                  # (else: launched by update(fused=True), with Adam)
             L.check(L.lib().gpi_step_epilogue(C.byref(self.epi), st), 'step epilogue')
@@ -465,9 +545,10 @@ class FusedElboStep(object):
         subsets, accumulators, gradient, the workspace (incl. the pre-drawn noise) and the term /
         statistics scratch."""
         ws = self.engine.ws
+        l2 = [] if self.l2 is None else [self.pen_grad, self.l2_norms, self.l2_pen, self.last_pen, self.l2_done]
         return [self.flat.P, self.m, self.v, self.step_ctr, self.rng_off, self.idx, self.idx_next, self.done_ctr,
                 self.handoff_flags, self.side_done,
-                self.flat.gacc, self.flat.G, ws.t_ws, ws.t_scr, ws.t_parts, ws.t_flag, self.last_terms] + \
+                self.flat.gacc, self.flat.G, ws.t_ws, ws.t_scr, ws.t_parts, ws.t_flag, self.last_terms] + l2 + \
             self.engine.running.buffers
 
     def capture(self, unroll=1):
@@ -623,8 +704,7 @@ class FusedElboStep(object):
         early = self.subset_early and bool(e.roms)
         e.side_pre = (lambda sst: self._launch_subset(sst, self.idx_next)) if early else None
         extra = {'forward_a': dict(zero_gacc=False, zero_scratch=False),
-                 'backward_side_a': dict(side_extra=lambda sst: self._launch_noise(
-                     sst, self.idx_next, codecs=('dec',), subset=not early))}
+                 'backward_side_a': dict(side_extra=lambda sst: self._side_extra(sst, early))}
 
         def tail(st):
             fused = self.fuse_adam
@@ -716,12 +796,20 @@ class FusedElboStep(object):
         self._post_error_copy()
 
     def elbo(self):
-        """ELBO value of the last completed step (0-d tensor)."""
-        return self.engine.elbo_value(self.last_terms)
+        """ELBO value of the last completed step (0-d tensor), less the step's L2 penalty (data parallel: on rank 0
+        alone, so the ranks' values still sum to the global objective)."""
+        val = self.engine.elbo_value(self.last_terms)
+        if self.l2 is not None and self.rank == 0:
+            val = (val.double() - self.last_pen[1]).to(torch.float32)
+        return val
 
     def terms(self):
-        """The individual ELBO terms of the last completed step (ElboEngine.terms; host sync)."""
-        return self.engine.terms(self.last_terms)
+        """The individual ELBO terms of the last completed step (ElboEngine.terms; host sync); with an L2 penalty
+        also 'elbo_l2_penalty', the sum of the parameter norms (the reference's scalar tag)."""
+        out = self.engine.terms(self.last_terms)
+        if self.l2 is not None:
+            out['elbo_l2_penalty'] = float(self.last_pen[0])
+        return out
 
     # ------------------------------------------------------------------ virtual observables
     def _require_vo(self, what):

@@ -550,7 +550,7 @@ int gpi_predictive_scores(const float* Y, const float* mean, const float* std, i
  * training.py:254,417.  step and lr are read from device memory so the
  * update can be replayed from a captured graph. */
 typedef struct gpi_adam_desc {
-    float* p; const float* g; float* m; float* v;
+    float* p; float* g; float* m; float* v;
     int64_t n;
     const float* lr;           /* device scalar */
     const int64_t* step;       /* device scalar: step number after increment */
@@ -565,6 +565,11 @@ typedef struct gpi_adam_desc {
      * -> some rank's hand-off timed out: this rank skips the update too and sets its own *wait_err, so every
      * rank keeps identical parameters and raises. */
     const float* skip_if;
+    /* optional (data-parallel steps with an L2 penalty, gpi_param_norms): the penalty's fp32 gradient joins the
+     * all-reduced gradient here, once on every rank, after the SUM: g[i] = g[i] + pen_grad[i] for i < pen_n is
+     * stored back (g is written then) and is the gradient of the update.  NULL / 0: g is only read. */
+    const float* pen_grad;
+    int64_t pen_n;
 } gpi_adam_desc;
 
 /* ---------------------------------------------------------------- API */
@@ -800,6 +805,15 @@ typedef struct gpi_step_epilogue_desc {
      * so after the SUM every rank sees whether ANY rank's hand-off timed out (gpi_adam_desc.skip_if).
      * -1: none. */
     int64_t err_slot;
+    /* optional L2 penalty of the step (gpi_param_norms): the finalised gradient of element i < pen_n is
+     * (float) gacc[i] + pen_grad[i] -- the penalty's gradient, already rounded to fp32, enters the flat gradient
+     * of -ELBO with a plus sign and never the fp64 accumulator.  pen_src: the two doubles {pen, lambda * pen}
+     * gpi_param_norms left for this step, saved to pen_dst in this launch, next to the step's terms.
+     * NULL / 0: no penalty, the launch does what it did without these fields.  pen_n <= n. */
+    const float* pen_grad;
+    int64_t pen_n;
+    const double* pen_src;
+    double* pen_dst;
 } gpi_step_epilogue_desc;
 int gpi_step_epilogue(const gpi_step_epilogue_desc* d, void* stream);
 int gpi_adam(const gpi_adam_desc* d, void* stream);
@@ -996,6 +1010,36 @@ typedef struct gpi_gpmlp_sample_desc {
     float* x;                                  /* [rows, d_x] out */
 } gpi_gpmlp_sample_desc;
 int gpi_gpmlp_sample(const gpi_gpmlp_sample_desc* d, void* stream);
+
+/* The l2_penalty of model.elbo (generative.py:268-278): the ELBO loses lambda * sum_s ||p_s||_2, the plain
+ * 2-norms of the penalised parameter tensors, each a segment [offset, offset + numel) of the flat fp32 buffer.
+ * ONE launch, one workgroup per segment, no host synchronisation (graph-capturable):
+ *   norms[s]          = ||p_s||_2 (fp64: the squares are exact in fp64; each lane adds its elements in index
+ *                       order, then a fixed-shape wave reduction and a fixed-order sum over the waves)
+ *   pen[0]            = sum_s norms[s], added in segment order by the last workgroup to finish (no atomics on
+ *                       the value), pen[1] = (double) *lambda * pen[0]
+ *   pen_grad[off + i] = (float) (*lambda * p[off + i] / norms[s]): the penalty's gradient, 0 for a segment whose
+ *                       norm is exactly 0 (torch.norm's backward), rounded once to fp32
+ * Two launches on the same inputs give the same bits.  pen_grad is dense over the flat prefix [0, pen_n) and is
+ * written at penalised elements only (zero it once: gpi_step_epilogue adds it to the gradient); p is read at
+ * penalised elements only.  lambda is a device scalar, read at launch: a captured launch follows an edit.
+ * seg: device table [n_seg][2] of (offset, numel); seg_host: the same table in host memory, read by this call
+ * only (the refusals below; the kernel also skips a segment outside [0, pen_n), norm NaN).  done: a device
+ * uint32 arrival counter, zero before the first call (the launch leaves it zero).
+ * GPI_ERR_ARG: n_seg <= 0, a NULL pointer, an offset < 0, numel < 1, a segment that ends past pen_n. */
+typedef struct gpi_param_norms_desc {
+    const float* p;
+    const int64_t* seg;
+    const int64_t* seg_host;
+    int32_t n_seg, _pad;
+    int64_t pen_n;
+    const float* lambda;       /* device scalar */
+    double* norms;             /* [n_seg] */
+    double* pen;               /* [2] */
+    float* pen_grad;           /* [pen_n] */
+    uint32_t* done;
+} gpi_param_norms_desc;
+int gpi_param_norms(const gpi_param_norms_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

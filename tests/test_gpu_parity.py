@@ -29,9 +29,24 @@ def rel(a, b):
 
 
 # ---------------------------------------------------------------- ROM
+def rom_c32_oracle(d):
+    """The fp64 oracle on rom_c32.npz's inputs (nc = 4, r = 8) -> (mu, logL, d(-logL)/dx, d(-logL)/dlogsigma_y)."""
+    from elbo_ref import physics
+    t = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+    M, W, bc = physics(4, 8)
+    e64, ls64 = t(d['effprop']).requires_grad_(), t(d['logsigmas_y']).requires_grad_()
+    mu, ls = oelbo.rom_operator(t(W), t(M), torch.as_tensor(bc), e64, t(d['F']), ls64)
+    Lo = oelbo.dgll(t(d['Y']), mu, 2 * ls)
+    (-Lo).backward()
+    return mu.detach().numpy(), Lo.item(), e64.grad.numpy(), ls64.grad.numpy()
+
+
 def test_rom_operator_forward_backward(device):
+    """nc = 4 (rom_kernel_fast<4, 256>): vs the reference's fp32 run (rom_c32.npz) and, at the project's bars
+    (mu 1e-5, value 1e-5, d/dx 1e-4, d/dlogsigma_y 1e-5), vs the fp64 oracle on the same inputs."""
     from gpi.native import RomOperatorFunction
     d = load('rom_c32.npz')
+    mu_o, L_o, gx_o, gls_o = rom_c32_oracle(d)
     x = cuda(d['effprop']).requires_grad_(True)
     F = cuda(d['F'])
     mu, uc = RomOperatorFunction.apply(x, F, 4, 8, False)
@@ -43,12 +58,18 @@ def test_rom_operator_forward_backward(device):
     assert abs(L.item() - float(d['logL'])) / abs(float(d['logL'])) < 1e-5
     assert rel(x.grad.cpu(), d['grad_effprop']) < 1e-3
     assert rel(ls.grad.cpu(), d['grad_logsigmas_y']) < 1e-4
+    assert rel(mu.detach().cpu(), mu_o) < 1e-5
+    assert abs(L.item() - L_o) <= 1e-5 * abs(L_o)
+    assert rel(x.grad.cpu(), gx_o) < 1e-4
+    assert rel(ls.grad.cpu(), gls_o) < 1e-5
 
 
 def test_rom_fused_loglik(device):
+    """gpi_rom ROM_LOGLIK at nc = 4: vs the reference's fp32 run and, at the project's bars, vs the fp64 oracle."""
     from gpi.engine import rom_call
     from gpi import _lib as L
     d = load('rom_c32.npz')
+    _, L_o, gx_o, gls_o = rom_c32_oracle(d)
     x, F, Y, ls = cuda(d['effprop']), cuda(d['F']), cuda(d['Y']), cuda(d['logsigmas_y'])
     gx = torch.zeros_like(x)
     gls = torch.zeros(ls.shape[0], dtype=torch.float64, device='cuda')
@@ -59,6 +80,9 @@ def test_rom_fused_loglik(device):
     assert rel(gx.cpu(), d['grad_effprop']) < 1e-3
     assert rel(gls.cpu(), d['grad_logsigmas_y']) < 1e-4
     assert flag.item() == 0
+    assert abs(acc.sum().item() - L_o) <= 1e-5 * abs(L_o)
+    assert rel(gx.cpu(), gx_o) < 1e-4
+    assert rel(gls.cpu(), gls_o) < 1e-5
 
 
 def test_rom_call_matches_reference_semantics(device):
